@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the batched ML-DSA hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already
 resident in HBM.  For N > 1 the driver launches one rank per GPU (torch.distributed.run);
@@ -14,14 +14,23 @@ Workloads (BASELINE.json configs):
   verify_arith44  config[1]: ml_dsa_44, batch 4096, NTT/INTT + pointwise kernels only
                   (the fused verify-arithmetic unit; the HBM-roofline kernel)
 
-Rank 0 prints ONE JSON line of at most 6 000 bytes (benchlib/line.py): the contract's keys,
-"roofline" (dominant kernel, HIP-event timed on the launch stream inside the timed region),
-"cpu_baseline" (the KAT-pinned CPU oracle timed on this box's host cores, rank 0, N = 1) and,
-in the default run, a compact "also" for sign65 and verify_arith44.  Everything else -- stage
-tables, by-stage rooflines, the Keccak-ceiling derivation, host-fed legs and, with --full, the
-corrupted / from-wire-bytes variants and the batch-size sweep with its CPU crossover -- goes to
-the side file named in the line ("extras_file": bench_extras.json beside this script).
-The parts live in benchlib/ (workloads, cpu, pmc, runner, sweep, group, line); this file is the CLI.
+Rank 0 prints ONE JSON line of at most 6 000 bytes (benchlib/line.py).  A plain run does only what
+that line's headline figure needs: it sets the workload up, runs the clock ramp and the W warm-up
+steps, times exactly K steps, writes the outputs of the last timed step when --dump-outputs is given,
+and prints the contract's keys ("roofline" is null: per-kernel times need a pass of their own).
+
+--full adds everything else, as before: the check of the workload against the CPU oracle, the live
+PMC passes, "roofline" (dominant kernel, HIP-event timed on the launch stream in a profiled pass of
+the same K steps), "cpu_baseline" (the KAT-pinned CPU oracle timed on this box's host cores, rank 0,
+N = 1) and, for the default workload, a compact "also" for sign65 and verify_arith44.  Stage tables,
+by-stage rooflines, the Keccak-ceiling derivation, host-fed legs, the corrupted / from-wire-bytes
+variants and the batch-size sweep with its CPU crossover go to the side file named in the line
+("extras_file": bench_extras.json beside this script).
+
+--dump-outputs DIR: what the timed path returned in its last step (verify: the verdicts; sign: the
+signatures and statuses; ...) as DIR/<name>.npy, float32 / float64, at most 64 MB (benchlib/dump.py).
+The inputs depend on the arguments only, so two builds can be compared output for output.
+The parts live in benchlib/ (workloads, cpu, pmc, runner, sweep, group, line, dump); this file is the CLI.
 """
 import argparse
 import json
@@ -47,15 +56,18 @@ def parse(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="only --workload: no also.sign65 / also.verify_arith44, no live PMC passes")
     ap.add_argument("--full", action="store_true",
-                    help="default run + the 1 %-corrupted verify batch, the from-wire-bytes units, host-fed legs and the batch-size sweep; "
-                         "all of it in the side file, the printed line stays the compact one")
-    ap.add_argument("--extras-file", default=bline.EXTRAS_FILE, help="name of the side file (beside bench.py; '' = do not write one)")
+                    help="everything beyond the headline figure: the oracle check, live PMC passes, the profiled pass and roofline, the CPU "
+                         "baseline, the side file and, for verify65, also{sign65, verify_arith44}, the 1 %%-corrupted verify batch, the "
+                         "from-wire-bytes units, host-fed legs and the batch-size sweep (side file); the printed line stays the compact one")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--extras-file", default=bline.EXTRAS_FILE, help="name of the side file of a --full run (beside bench.py; '' = do not write one)")
     ap.add_argument("--backend", default=os.environ.get("MLDSA_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend of the N > 1 run: nccl (= RCCL) or gloo (CPU rendezvous; lets several ranks "
                          "share one GPU for a functional check on a 1-GPU box)")
     ap.add_argument("--graphs", type=int, default=-1, help="override MLDSA_OPT_GRAPHS (hipGraph replay) of the context: 0 / 1")
     ap.add_argument("--pmc", action="store_true", help="measure roofline.traffic live for --workload (two child rocprofv3 counter passes); "
-                                                       "the default run does this for verify65 unless --no-pmc")
+                                                       "a --full run does this for verify65 unless --no-pmc")
     ap.add_argument("--no-pmc", action="store_true", help="never start the profiler: roofline.traffic from this round's file under profiles/ (null when absent)")
     ap.add_argument("--resident", action="store_true",
                     help="with --inproc: slices resident per device and the device-resident group calls (mldsa_verify_group / mldsa_sign_group): "
@@ -75,9 +87,10 @@ def early_pmc(args):
     if args.inproc or (args.gpus > 1 and "RANK" not in os.environ):
         return
     single = args.gpus == 1 and "RANK" not in os.environ
-    if single and not args.no_pmc and (args.pmc or (args.workload == "verify65" and not args.no_extras)):
-        # the headline workload, and in the default run config[1]'s kernel too (also.verify_arith44.traffic_ratio: PMC bytes / algorithmic bytes)
-        for name in (args.workload,) + (("verify_arith44",) if args.workload == "verify65" and not args.no_extras else ()):
+    with_also = args.full and args.workload == "verify65" and not args.no_extras
+    if single and not args.no_pmc and (args.pmc or with_also):
+        # the headline workload, and in the --full run config[1]'s kernel too (also.verify_arith44.traffic_ratio: PMC bytes / algorithmic bytes)
+        for name in (args.workload,) + (("verify_arith44",) if with_also else ()):
             got = measure_pmc_traffic(name)
             if got:
                 LIVE_PMC[name] = got
@@ -101,7 +114,7 @@ from benchlib.sweep import SWEEP_SIZES, run_single_op_callers, run_small_calls, 
 from benchlib.workloads import MixedStream, SeamKernel, VerifyArith, WholeOp, config5_requests, make_workload  # noqa: E402,F401
 
 
-# (workload, steps, warmup, CPU-baseline budget in seconds) of the default run's `also` objects
+# (workload, steps, warmup, CPU-baseline budget in seconds) of the --full run's `also` objects
 # (the GPU idles for seconds while the previous workload's CPU baseline runs and its clocks drop: the warm-ups are long enough to bring
 #  them back before a timed region starts -- config[1]'s kernel runs 26 us a step, so its 500 warm-up steps are 13 ms)
 ALSO_DEFAULT = (("sign65", 30, 6, 6.0), ("verify_arith44", 2000, 500, 3.0))
@@ -132,6 +145,8 @@ def run_sweep_workload(args, hp, multi_gpu):
 
 def main():
     args = _ARGS if _ARGS is not None else parse()
+    if args.dump_outputs and (args.inproc or args.workload == "sweep"):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the resident single-workload path; not with --inproc or --workload sweep")
     if args.inproc:
         return run_inproc_resident(args) if args.resident else run_inproc(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -146,29 +161,29 @@ def main():
     hp = HotPath(local_rank)
     if args.graphs >= 0:
         hp.set_option(1, args.graphs)
-    default_run = world == 1 and args.workload == "verify65" and not args.no_extras
+    default_run = args.full and world == 1 and args.workload == "verify65" and not args.no_extras
     if args.workload == "sweep":
         if world != 1:
             raise SystemExit("bench.py: --workload sweep is a single-GPU measurement")
         return run_sweep_workload(args, hp, multi_gpu)
-    cb = not args.no_cpu_baseline
+    cb = args.full and not args.no_cpu_baseline
     full = run_one(args, hp, rank, world, args.workload, args.steps, args.warmup, cb,
-                   with_host_fed=(default_run and args.full) or os.environ.get("MLDSA_BENCH_HOST_FED") == "1")
-    # the default single-GPU run also carries BASELINE config[2] (whole sign) and config[1] (the HBM-roofline kernel) as compact
-    # `also` objects; --full adds the SURVEY 8(d) variants and the sweep -- to the side file only
+                   with_host_fed=default_run or os.environ.get("MLDSA_BENCH_HOST_FED") == "1", full=args.full, dump_dir=args.dump_outputs or None)
+    # the --full single-GPU run also carries BASELINE config[2] (whole sign) and config[1] (the HBM-roofline kernel) as compact
+    # `also` objects, and the SURVEY 8(d) variants and the sweep -- those to the side file only
     also, extras = {}, {}
     if default_run:
-        for name, st, wu, budget in ALSO_DEFAULT + (ALSO_FULL if args.full else ()):
-            sub = run_one(args, hp, rank, world, name, st, wu, cb and budget > 0, with_host_fed=(args.full and name == "sign65"), cpu_budget_s=budget or None)
+        for name, st, wu, budget in ALSO_DEFAULT + ALSO_FULL:
+            sub = run_one(args, hp, rank, world, name, st, wu, cb and budget > 0, with_host_fed=(name == "sign65"), cpu_budget_s=budget or None)
             (also if (name, st, wu, budget) in ALSO_DEFAULT else extras)[name] = sub
-        if args.full:
-            extras["sweep"] = run_sweep(hp, cpu=cb)
+        extras["sweep"] = run_sweep(hp, cpu=cb)
     if rank == 0:
-        line = bline.compact_line(full, also, extras_file=args.extras_file or None)
-        if args.extras_file:
+        extras_file = args.extras_file if args.full else ""
+        line = bline.compact_line(full, also, extras_file=extras_file or None)
+        if extras_file:
             side = {"headline": full, "also": also, **extras, "library_stats": hp.stats(), "argv": sys.argv[1:],
                     "wall_s": time.perf_counter() - t_start}
-            bline.write_extras(ROOT, side, args.extras_file)
+            bline.write_extras(ROOT, side, extras_file)
         bline.emit(line)
     hp.close()
     multi_gpu.finish()

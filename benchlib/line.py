@@ -69,7 +69,7 @@ def compact_line(full, also=None, extras_file=EXTRAS_FILE):
     cfg = full.get("config", {})
     line["config"] = {"workload": short_workload(cfg.get("workload", "")), "batch_per_gpu": cfg.get("batch_per_gpu"),
                       "parallelism": _short(cfg.get("parallelism", ""))}
-    line["roofline"] = compact_roofline(full)
+    line["roofline"] = compact_roofline(full) if full.get("roofline") else None   # (None: a plain run, no profiled pass)
     cb = compact_cpu(full)
     if cb:
         line["cpu_baseline"] = cb

@@ -95,13 +95,16 @@ def timed_steps(wl, world, steps, first, marks=64):
     return max_over_ranks(dt, world), evs[0].elapsed_time(ev_end)
 
 
-def run_one(args, hp, rank, world, name, steps, warmup, cpu_baseline, with_host_fed=False, cpu_budget_s=None):
+def run_one(args, hp, rank, world, name, steps, warmup, cpu_baseline, with_host_fed=False, cpu_budget_s=None, full=True, dump_dir=None):
+    """full = False (a plain bench.py run): set-up, clock ramp, warm-up and the K timed steps only -- no check against the oracle, no clock
+    reads, no profiled pass, no verdict gather, no CPU baseline; the object carries the contract's keys and the spread of the timed steps.
+    dump_dir: rank 0 writes what the last timed step computed there (benchlib/dump.py)."""
     wl = make_workload(name, hp, args.batch if name == args.workload else 0, rank, world)
-    if rank == 0:
+    if rank == 0 and full:
         wl.check()
     # (outside steps / warmup; in the side file.  Nothing but the warm-up, a synchronize and the barrier lies between the ramp and the timed
     #  region: no file is read, no object is built there)
-    ramp, sclk0 = clock_ramp(wl, 0, min_ms=float(os.environ.get("BENCH_RAMP_MS", "200")), midway=read_sclk if rank == 0 else None)
+    ramp, sclk0 = clock_ramp(wl, 0, min_ms=float(os.environ.get("BENCH_RAMP_MS", "200")), midway=read_sclk if rank == 0 and full else None)
     for i in range(warmup):
         wl.step(i)
     torch.cuda.synchronize()
@@ -110,12 +113,15 @@ def run_one(args, hp, rank, world, name, steps, warmup, cpu_baseline, with_host_
 
     # THE timed region: exactly K steps of the product's default path (a signing call whose shape repeats replays as a
     # hipGraph), barrier + synchronize on both sides, max over ranks -> `value`
-    st0 = hp.stats() if hasattr(hp, "stats") else None
+    st0 = hp.stats() if full and hasattr(hp, "stats") else None
     dt, ev_ms = timed_steps(wl, world, steps, warmup)
+    if dump_dir and rank == 0:  # the last timed step's results, before anything else runs on the workload's buffers
+        from . import dump
+        dump.write(dump_dir, dump.to_host(wl.outputs()))
     step_ms = timed_steps.step_ms
     marks_ms = getattr(timed_steps, "marks_ms", None)
     enqueue_ms = getattr(timed_steps, "enqueue_ms", None)
-    sclk1 = read_sclk() if rank == 0 else None
+    sclk1 = read_sclk() if rank == 0 and full else None
     kern_ms = ev_ms / steps / wl.kernel_launches_per_step()
     value = units_per_step * world * steps / dt
     ranks = None
@@ -123,6 +129,20 @@ def run_one(args, hp, rank, world, name, steps, warmup, cpu_baseline, with_host_
         from .dist import min_over_ranks
         mine = units_per_step * steps / timed_steps.local_s
         ranks = {"min": min_over_ranks(mine, world), "max": max_over_ranks(mine, world), "unit": wl.unit + " per rank"}
+    if not full:
+        if rank != 0:
+            return None
+        line = {"metric": wl.metric, "value": value, "unit": wl.unit, "n_gpus": world, "steps": steps,
+                "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": wl.dtype, "data": "synthetic",
+                "config": {"workload": wl.name, "batch_per_gpu": wl.batch, "parallelism": f"batch-split x{world}",
+                           "input_sets_rotated": wl.n_sets},
+                "roofline": None}  # (per-kernel times need the profiled pass: --full)
+        if step_ms:
+            line["step_ms"] = step_ms
+        if ranks:
+            line["ranks"] = ranks
+        return line
     st1 = hp.stats()
     launch_mode = {"graph_replays": st1["graph_replays"] - st0["graph_replays"], "direct_calls": st1["direct_calls"] - st0["direct_calls"],
                    "sign_extra_rounds": st1["sign_extra_rounds"] - st0["sign_extra_rounds"]}

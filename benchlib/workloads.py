@@ -59,6 +59,10 @@ class VerifyArith:
     def kernel_launches_per_step(self):
         return 1
 
+    def outputs(self):
+        """what a caller of the timed path receives from the last step: w' of every op"""
+        return {"w_prime": self.out}
+
     def check(self):
         from oracle import oracle as orc
         a, z, c, t1 = self.inputs[0]
@@ -147,10 +151,16 @@ class SeamKernel:
         self.metric = f"{name} {self.unit} per GPU (batched); % HBM roofline"
 
     def step(self, i):
-        self.call(i)
+        self.last = self.call(i)
 
     def kernel_launches_per_step(self):
         return 1
+
+    def outputs(self):
+        """what the last step's call returned (keygen: the wire-format keys)"""
+        if isinstance(self.last, tuple):
+            return {"pk": self.last[0], "sk": self.last[1]}
+        return {self.name_: self.last}
 
     def check(self):
         """the first ops of the very buffers the timed region uses, against the oracle (bit-exact)"""
@@ -318,6 +328,12 @@ class WholeOp:
 
     def kernel_launches_per_step(self):
         return 1
+
+    def outputs(self):
+        """what a caller of the timed path receives from the last step: the verdicts, or the signatures and their statuses"""
+        if self.kind == "verify":
+            return {"verdicts": self.ok}
+        return {"signatures": self.sigs, "status": self.status}
 
     def _oracle_keys(self, n):
         from oracle import oracle as orc
@@ -489,6 +505,19 @@ class MixedStream:
 
     def kernel_launches_per_step(self):
         return 1
+
+    def outputs(self):
+        """what the nine calls of the last step returned: per set the generated keys, the signatures with their statuses, the verdicts"""
+        out = {}
+        for d in self.sets:
+            ps, s, v = d["ml"].pset, d["sign"], d["verify"]
+            if len(d["kg_xi_host"]):
+                out[f"keygen{ps}_pk"], out[f"keygen{ps}_sk"] = d["kg_pk"], d["kg_sk"]
+            if s["n"]:
+                out[f"sign{ps}_signatures"], out[f"sign{ps}_status"] = s["sig"][:s["n"]], s["st"][:s["n"]]
+            if v["n"]:
+                out[f"verify{ps}_verdicts"] = v["ok"][:v["n"]]
+        return out
 
     def finish_steps(self):
         """mldsa_sign_async plans its rounds until an unfinished op is unlikely and reports one as MLDSA_ERR_AGAIN; the stream

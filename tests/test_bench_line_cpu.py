@@ -137,3 +137,43 @@ def test_line_carries_the_spread_of_the_timed_steps_and_the_side_object_the_cloc
     # profiler session ran in another process, the first deep burst of launches ran slowly: the first dozen steps of the timed region)
     bsrc = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")).read()
     assert bsrc.index("early_pmc(_ARGS)") < bsrc.index("\nimport torch")
+
+
+def test_dump_outputs_are_exact_floats_within_the_budget(tmp_path):
+    """--dump-outputs: every array as float32 / float64 holding every value exactly; over the budget, one fixed seeded row sample
+    shared by the arrays (row numbers beside them), the same on every run"""
+    import numpy as np
+    from benchlib import dump
+    rng = np.random.default_rng(7)
+    sigs = rng.integers(0, 256, (65536, 3309), dtype=np.uint8)
+    status = rng.integers(-5, 1, 65536, dtype=np.int32)
+    w = np.full((16, 4, 256), 8380416, dtype=np.int32)
+    got = dump.write(str(tmp_path / "a"), {"signatures": sigs, "status": status})
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= dump.MAX_BYTES
+    rows = np.load(tmp_path / "a" / "signatures_rows.npy").astype(np.int64)
+    assert got["signatures"] == [rows.size, 3309] and np.array_equal(rows, np.load(tmp_path / "a" / "status_rows.npy"))
+    s = np.load(tmp_path / "a" / "signatures.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, sigs[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), status[rows])
+    dump.write(str(tmp_path / "b"), {"signatures": sigs, "status": status})
+    assert np.array_equal(np.load(tmp_path / "b" / "signatures_rows.npy"), rows)
+    dump.write(str(tmp_path / "c"), {"w_prime": w, "verdicts": np.ones(65536, dtype=np.uint8)})
+    assert sorted(os.listdir(tmp_path / "c")) == ["verdicts.npy", "w_prime.npy"]
+    x = np.load(tmp_path / "c" / "w_prime.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, w)
+
+
+def test_a_plain_run_is_lean_and_full_keeps_the_rest():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; the oracle check, clock reads, PMC passes,
+    CPU baseline, also{} and side file are behind --full"""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+    import inspect
+    from benchlib import runner
+    src = inspect.getsource(runner.run_one)
+    assert "if rank == 0 and full:\n        wl.check()" in src
+    assert src.index("timed_steps(wl, world, steps, warmup)") < src.index("dump.write(") < src.index("if not full:") < src.index("hp.profile_enable(True)")
+    msrc = inspect.getsource(bench.main)
+    assert "default_run = args.full and" in msrc and "cb = args.full and" in msrc

@@ -20,7 +20,7 @@ for v in $VARS; do
     for pass in "tcc:TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "sq:SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAVES"; do
       tag=${pass%%:*}; ctrs=${pass#*:}
       name=${tag}_${w}_$v
-      ( cd /tmp && rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d "$OUT/raw_$name" -o p -- python3 "$OLDPWD/bench.py" --workload $w --steps $steps --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file "" > "$OUT/$name.log" 2>&1 )
+      ( cd /tmp && rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d "$OUT/raw_$name" -o p -- python3 "$OLDPWD/bench.py" --full --workload $w --steps $steps --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file "" > "$OUT/$name.log" 2>&1 )
       python tools/pmc_summary.py sq $name "$OUT/raw_$name" $R > /dev/null 2>> "$OUT/errors.log"
       mv profiles/${R}_sq_$name.json "$OUT"/ 2>/dev/null
       rm -rf "$OUT/raw_$name" "$OUT/$name.log"

@@ -3,7 +3,7 @@
 
     python tools/ab_variants.py [--reps 2] [--variants base,1,2,...] [--workloads sign65,verify65,verify_arith44] [--out FILE]
 
-Every (rep, variant, workload) is one `python bench.py --workload W --no-extras --no-pmc --no-cpu-baseline` process with the variant's
+Every (rep, variant, workload) is one `python bench.py --full --workload W --no-extras --no-pmc --no-cpu-baseline` process with the variant's
 .so copied over fips204_amd/csrc/libmldsa_hip.so (restored at the end); the variants alternate inside a rep so that clock and box drift
 hit all of them alike.  bench.py's own check against the CPU oracle runs in every process: a variant that changes one byte fails here.
 Prints one line per run and a summary (median over reps) with the stage that should move; writes everything to --out.
@@ -26,7 +26,7 @@ STAGES = {"keygen65": (), "keygen44": (), "keygen87": (), "sign65": ("sign_w", "
 
 def run(workload, side):
     st, wu = STEPS[workload]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--no-extras", "--no-pmc", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--no-extras", "--no-pmc", "--no-cpu-baseline",
            "--steps", str(st), "--warmup", str(wu), "--extras-file", side]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -32,24 +32,23 @@ line() { f=$1; shift; "$@" 2>> "$ERR" | grep "^{" | tail -1 > "$OUT/$f"; note "$
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -2 > "$OUT/gpu_suite.txt"; note gpu_suite.txt "python -m pytest tests -m gpu -q  (summary line)"
 # ---- bench lines
 line bench_default.json python bench.py
-cp bench_extras.json "$OUT/bench_default_extras.json" 2>/dev/null && note bench_default_extras.json "python bench.py  (the side file named in the line)"
 line bench_full.json python bench.py --full
 cp bench_extras.json "$OUT/bench_full_extras.json" 2>/dev/null && note bench_full_extras.json "python bench.py --full  (side file: corrupted / wire variants, host-fed legs, sweep)"
-line bench_sign65.json python bench.py --workload sign65 --no-extras
-line bench_verify_arith44.json python bench.py --workload verify_arith44 --steps 500 --warmup 20 --pmc
+line bench_sign65.json python bench.py --full --workload sign65 --no-extras
+line bench_verify_arith44.json python bench.py --full --workload verify_arith44 --steps 500 --warmup 20 --pmc
 : > "$OUT/bench_other_workloads.jsonl"
 for w in verify44 verify87 sign44 sign87 keygen44 keygen65 keygen87 mixed ntt inv_ntt mat_vec_mul65 expand_a65 expand_mask65 verify65_cached_a sign65_cached_a verify65_wire sign65_wire verify65_corrupt1; do
-  python bench.py --workload $w --no-extras --no-pmc --extras-file "" $( case $w in verify44|verify87|sign44|sign87|keygen65|mixed) ;; *) echo --no-cpu-baseline ;; esac ) 2>> "$ERR" | grep "^{" | tail -1 >> "$OUT/bench_other_workloads.jsonl"
+  python bench.py --full --workload $w --no-extras --no-pmc --extras-file "" $( case $w in verify44|verify87|sign44|sign87|keygen65|mixed) ;; *) echo --no-cpu-baseline ;; esac ) 2>> "$ERR" | grep "^{" | tail -1 >> "$OUT/bench_other_workloads.jsonl"
 done
-note bench_other_workloads.jsonl "for w in verify44 ... verify65_corrupt1: python bench.py --workload \$w --no-extras --no-pmc [--no-cpu-baseline]"
-line bench_config4_slice.json python bench.py --workload verify87 --batch 131072 --no-cpu-baseline --steps 10 --no-extras --no-pmc --extras-file ""
-line bench_mixed_65536.json python bench.py --workload mixed --batch 65536 --no-cpu-baseline --steps 5 --warmup 2 --no-extras --no-pmc --extras-file ""
+note bench_other_workloads.jsonl "for w in verify44 ... verify65_corrupt1: python bench.py --full --workload \$w --no-extras --no-pmc [--no-cpu-baseline]"
+line bench_config4_slice.json python bench.py --full --workload verify87 --batch 131072 --no-cpu-baseline --steps 10 --no-extras --no-pmc --extras-file ""
+line bench_mixed_65536.json python bench.py --full --workload mixed --batch 65536 --no-cpu-baseline --steps 5 --warmup 2 --no-extras --no-pmc --extras-file ""
 line sweep_batch_sizes.json python bench.py --workload sweep --extras-file sweep_extras.json
 cp sweep_extras.json "$OUT/sweep_batch_sizes_extras.json" 2>/dev/null && note sweep_batch_sizes_extras.json "python bench.py --workload sweep  (side file: every point, CPU and reference-published crossovers, single-op callers)"
 # ---- the multi-rank and in-library group paths on this 1-GPU box (functional)
-line bench_gpus2_gloo_shared_gpu.json python bench.py --gpus 2 --backend gloo --workload verify87 --batch 32768 --no-cpu-baseline --steps 5 --no-pmc --extras-file ""
-MLDSA_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 python bench.py --gpus 1 --workload verify87 --batch 32768 --no-cpu-baseline --steps 5 --no-pmc --no-extras --extras-file "" 2>> "$ERR" | grep "^{" | tail -1 > "$OUT/bench_rccl_world1.json"
-note bench_rccl_world1.json "MLDSA_BENCH_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 python bench.py --gpus 1 --workload verify87 --batch 32768 (RCCL code path, world of one)"
+line bench_gpus2_gloo_shared_gpu.json python bench.py --full --gpus 2 --backend gloo --workload verify87 --batch 32768 --no-cpu-baseline --steps 5 --no-pmc --extras-file ""
+MLDSA_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 python bench.py --full --gpus 1 --workload verify87 --batch 32768 --no-cpu-baseline --steps 5 --no-pmc --no-extras --extras-file "" 2>> "$ERR" | grep "^{" | tail -1 > "$OUT/bench_rccl_world1.json"
+note bench_rccl_world1.json "MLDSA_BENCH_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 python bench.py --full --gpus 1 --workload verify87 --batch 32768 (RCCL code path, world of one)"
 line inproc_resident_verify87_8ctx_on_1gpu_functional.json python bench.py --inproc --resident --gpus 8 --workload verify87 --batch 131072 --steps 5 --warmup 2
 line inproc_group2_verify65_hostfed.json python bench.py --inproc --gpus 2 --workload verify65 --batch 32768 --steps 5 --warmup 1
 python tools/config4_full.py "$OUT/config4_full_2pow20_8ctx_on_1gpu_functional.json" > /dev/null 2>> "$ERR"; note config4_full_2pow20_8ctx_on_1gpu_functional.json "python tools/config4_full.py"
@@ -59,18 +58,18 @@ python tools/scale_preflight.py 2>> "$ERR" | tail -1 > "$OUT/scale_preflight_1gp
 # ---- rocprofv3 per-kernel summaries of the commands whose kernel times bench.py reports
 for spec in "verify65:--no-extras" "sign65:--workload sign65 --no-extras --steps 30 --warmup 3" "default:"; do
   tag=${spec%%:*}; flags=${spec#*:}
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$tag" -o r -- python3 "$OLDPWD/bench.py" --no-cpu-baseline --no-pmc --extras-file "" $flags > "$OUT/prof_$tag.log" 2>&1 )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$tag" -o r -- python3 "$OLDPWD/bench.py" --full --no-cpu-baseline --no-pmc --extras-file "" $flags > "$OUT/prof_$tag.log" 2>&1 )
   find "$OUT/prof_$tag" -name "*kernel_stats.csv" -exec cp {} "$OUT/rocprofv3_kernel_stats_$tag.csv" \;
   rm -rf "$OUT/prof_$tag" "$OUT/prof_$tag.log"
-  note rocprofv3_kernel_stats_$tag.csv "cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-pmc $flags"
+  note rocprofv3_kernel_stats_$tag.csv "cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-pmc $flags"
 done
 # ---- HBM traffic (FETCH_SIZE / WRITE_SIZE, separate passes)
 for w in verify65 verify_arith44 sign65; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp && rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_${w}_$c" -o p -- python3 "$OLDPWD/bench.py" --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file "" > /dev/null 2>&1 )
+    ( cd /tmp && rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_${w}_$c" -o p -- python3 "$OLDPWD/bench.py" --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file "" > /dev/null 2>&1 )
   done
   python tools/pmc_summary.py hbm $w "$OUT/pmc_${w}_FETCH_SIZE" "$OUT/pmc_${w}_WRITE_SIZE" $R >> "$ERR" 2>&1
-  cp profiles/${R}_pmc_$w.json "$OUT/pmc_$w.json"; note pmc_$w.json "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --workload $w --steps 3 --no-extras --no-pmc; tools/pmc_summary.py hbm"
+  cp profiles/${R}_pmc_$w.json "$OUT/pmc_$w.json"; note pmc_$w.json "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --full --workload $w --steps 3 --no-extras --no-pmc; tools/pmc_summary.py hbm"
   rm -rf "$OUT"/pmc_${w}_FETCH_SIZE "$OUT"/pmc_${w}_WRITE_SIZE
 done
 # ---- SQ counters: the batch kernels, and the cooperative kernels of small calls (64-op calls: every launch is one of them)
@@ -81,9 +80,9 @@ sqpass() { # name, counters, program args...
   cp profiles/${R}_sq_$name.json "$OUT/sq_$name.json"; note sq_$name.json "rocprofv3 --pmc $ctrs --kernel-trace -- python3 $*; tools/pmc_summary.py sq"
   rm -rf "$OUT/sq_$name"
 }
-sqpass expand_a65 "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" "$PWD/bench.py" --workload expand_a65 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --extras-file ""
-sqpass sign65 "SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAVES" "$PWD/bench.py" --workload sign65 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file ""
-sqpass verify65 "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" "$PWD/bench.py" --workload verify65 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file ""
+sqpass expand_a65 "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" "$PWD/bench.py" --full --workload expand_a65 --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --extras-file ""
+sqpass sign65 "SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAVES" "$PWD/bench.py" --full --workload sign65 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file ""
+sqpass verify65 "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" "$PWD/bench.py" --full --workload verify65 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-pmc --extras-file ""
 for op in verify sign keygen; do
   sqpass coop_${op}_n64 "SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU" "$PWD/tools/latency_probe.py" $op 64 40
 done

@@ -15,9 +15,8 @@ PY
 note() { python3 -c 'import json,sys; print(json.dumps({"file": sys.argv[1], "command": sys.argv[2]}))' "$1" "$2" >> "$OUT/MANIFEST.jsonl"; }
 line() { f=$1; shift; "$@" 2>> "$OUT/stderr.log" | grep "^{" | tail -1 > "$OUT/$f"; note "$f" "$*  (bench.py as of the round's last commit)"; }
 line bench_default.json python bench.py
-cp bench_extras.json "$OUT/bench_default_extras.json" && note bench_default_extras.json "python bench.py  (the side file named in the line; bench.py as of the round's last commit)"
 line bench_full.json python bench.py --full
 cp bench_extras.json "$OUT/bench_full_extras.json" && note bench_full_extras.json "python bench.py --full  (side file: corrupted / wire variants, host-fed legs, sweep; bench.py as of the round's last commit)"
-line bench_verify_arith44.json python bench.py --workload verify_arith44 --steps 500 --warmup 20 --pmc
+line bench_verify_arith44.json python bench.py --full --workload verify_arith44 --steps 500 --warmup 20 --pmc
 line bench_driver_shape_steps20.json python bench.py --steps 20 --warmup 5
 ls -la "$OUT"

@@ -163,7 +163,7 @@ def rccl_report(import_torch=True):
 
 def run_bench(n, extra=()):
     """step 3: bench.py --gpus n as a child process (never an exec from a process that has touched the GPU)"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-pmc",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-pmc",
            "--no-extras", "--extras-file", ""] + list(extra)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
