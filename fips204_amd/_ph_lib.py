@@ -1,0 +1,62 @@
+"""ctypes loader for the pre-hash library (include/mldsa_ph.h, fips204_amd/ph/libmldsa_ph.so).
+
+The library is layered on the core (include/mldsa_hip.h): the core is loaded first, so that the pre-hash library's
+NEEDED libmldsa_hip.so resolves to the copy already in the process (one HIP module registration, one kind of
+mldsa_ctx).  There is no fallback: a missing library is an ImportError with a build hint.
+"""
+import ctypes as C
+import os
+
+from . import _lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "ph", "libmldsa_ph.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mldsa_ph.h")
+
+ABI_VERSION = 1
+PH_SHA256, PH_SHA512, PH_SHAKE128 = 0, 1, 2
+
+_P, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
+
+# name -> argtypes (all return int unless listed in _RESTYPES)
+_SIGNATURES = {
+    "mldsa_ph_abi_version": [],
+    "mldsa_ph_last_error": [],
+    "mldsa_ph_row_len": [_I],
+    "mldsa_ph_scratch_bytes": [_I, _SZ],
+    # ctx, ph, msgs, msg_off, out, bad, n_ops, stream
+    "mldsa_prehash": [_P, _I, _P, _P, _P, _P, _SZ, _P],
+    # ctx, set, ph, rho, tr, t1, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, sigs, ok, n_ops, scratch, scratch_bytes, stream
+    "mldsa_hash_verify": [_P, _I, _I, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P],
+    # ctx, set, ph, pk, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, sigs, ok, n_ops, scratch, scratch_bytes, stream
+    "mldsa_hash_verify_pk": [_P, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P],
+    # ctx, set, ph, rho, K, tr, s1, s2, t0, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, rnd, sigs, status, n_ops, scratch,
+    # scratch_bytes, stream
+    "mldsa_hash_sign": [_P, _I, _I] + [_P] * 6 + [_SZ] + [_P] * 8 + [_SZ, _P, _SZ, _P],
+}
+_RESTYPES = {"mldsa_ph_last_error": C.c_char_p, "mldsa_ph_scratch_bytes": _SZ}
+
+_lib_ph = None
+
+
+def load():
+    global _lib_ph
+    if _lib_ph is not None:
+        return _lib_ph
+    _lib.load()  # the core first: libmldsa_ph.so's NEEDED entry binds to it
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(
+            f"{LIB_PATH} is missing: build it with `python -m fips204_amd.build` "
+            "(make -C fips204_amd/ph after the core); there is no host fallback for the device pre-hash")
+    lib = C.CDLL(LIB_PATH)
+    for name, argtypes in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = _RESTYPES.get(name, C.c_int)
+    _lib_ph = lib
+    return lib
+
+
+def check(rc):
+    if rc != _lib.OK:
+        raise _lib.MldsaError(rc, load().mldsa_ph_last_error().decode(errors="replace"))

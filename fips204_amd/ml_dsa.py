@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _ph_lib
 from .hotpath import HotPath, N, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -20,6 +20,20 @@ MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
 # host work; the device sees OID || PH(M) as the message of a MODE_PREHASH call.
 PH_SHA256, PH_SHA512, PH_SHAKE128 = "SHA256", "SHA512", "SHAKE128"
 _PH_OID = bytes([0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x02])
+# the same pre-hash on the device (include/mldsa_ph.h): Ph -> MLDSA_PH_*; list-level calls choose with prehash="host" | "device"
+_PH_ABI = {PH_SHA256: _ph_lib.PH_SHA256, PH_SHA512: _ph_lib.PH_SHA512, PH_SHAKE128: _ph_lib.PH_SHAKE128}
+
+
+def _ph_code(ph):
+    if ph not in _PH_ABI:
+        raise ValueError("Ph: SHA256, SHA512 or SHAKE128")
+    return _PH_ABI[ph]
+
+
+def _check_prehash(prehash):
+    if prehash not in ("host", "device"):
+        raise ValueError('prehash: "host" or "device"')
+    return prehash == "device"
 
 
 class OsRng:
@@ -125,6 +139,11 @@ class MlDsa:
         `sigs`: uint8 CUDA tensor [n_ops, SIG_LEN] or a list of byte strings (a signature of
         the wrong length verifies as False, like a failed `try_into()` in the reference's
         callers).  `ctxs`: list of byte strings or None (= empty)."""
+        return self._verify_batch(pks, messages, sigs, ctxs, key_idx,
+                                  lambda *a: self.verify_device(pks, *a, mode=mode))
+
+    def _verify_batch(self, pks, messages, sigs, ctxs, key_idx, run):
+        """verify()'s host side around run(msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, key_idx)"""
         n_ops = len(messages)
         wrong_len = None
         if not isinstance(sigs, torch.Tensor):
@@ -142,16 +161,20 @@ class MlDsa:
         if key_idx is not None:
             kidx = torch.as_tensor(key_idx.view(np.int32)).to(self.device)
         ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
-        self.verify_device(pks, msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
+        run(msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, kidx)
         torch.cuda.synchronize(self.device)
         res = ok[:n_ops].cpu().numpy().astype(bool)
         if wrong_len is not None:
             res &= ~wrong_len
         return res
 
-    def hash_verify(self, pks, messages, sigs, ctxs=None, ph=PH_SHA512, key_idx=None):
+    def hash_verify(self, pks, messages, sigs, ctxs=None, ph=PH_SHA512, key_idx=None, prehash="host"):
         """PublicKey::hash_verify (src/traits.rs:361, src/lib.rs:391-411) for a batch: HashML-DSA.Verify with the
-        pre-hash `ph` computed on the host."""
+        pre-hash `ph` computed on the host (prehash="host") or on the device (prehash="device", mldsa_hash_verify)."""
+        if _check_prehash(prehash):
+            code = _ph_code(ph)
+            return self._verify_batch(pks, messages, sigs, ctxs, key_idx,
+                                      lambda *a: self.hash_verify_device(pks, *a[:5], code, *a[5:]))
         return self.verify(pks, [hash_message(m, ph) for m in messages], sigs, ctxs=ctxs, key_idx=key_idx, mode=MODE_PREHASH)
 
     def expand_a_for_keys(self, keys):
@@ -417,20 +440,26 @@ class MlDsa:
         """PrivateKey::try_sign (src/traits.rs:156-158): hedged signing with rnd from OsRng"""
         return self.try_sign_with_rng(OsRng(), sks, messages, ctxs=ctxs, key_idx=key_idx)
 
-    def try_hash_sign_with_rng(self, rng, sks, messages, ctxs=None, ph=PH_SHA512, key_idx=None):
+    def try_hash_sign_with_rng(self, rng, sks, messages, ctxs=None, ph=PH_SHA512, key_idx=None, prehash="host"):
         """PrivateKey::try_hash_sign_with_rng (src/lib.rs:310-342)"""
         if ctxs is not None and any(len(c) > 255 for c in ctxs):
             raise ValueError("HashML-DSA.Sign: ctx too long")
-        return self.try_hash_sign_with_seed(sks, messages, [rng.fill_bytes(32) for _ in messages], ctxs=ctxs, ph=ph, key_idx=key_idx)
+        return self.try_hash_sign_with_seed(sks, messages, [rng.fill_bytes(32) for _ in messages], ctxs=ctxs, ph=ph, key_idx=key_idx,
+                                            prehash=prehash)
 
-    def try_hash_sign(self, sks, messages, ctxs=None, ph=PH_SHA512, key_idx=None):
+    def try_hash_sign(self, sks, messages, ctxs=None, ph=PH_SHA512, key_idx=None, prehash="host"):
         """PrivateKey::try_hash_sign (src/traits.rs:247-251)"""
-        return self.try_hash_sign_with_rng(OsRng(), sks, messages, ctxs=ctxs, ph=ph, key_idx=key_idx)
+        return self.try_hash_sign_with_rng(OsRng(), sks, messages, ctxs=ctxs, ph=ph, key_idx=key_idx, prehash=prehash)
 
     def try_sign_with_seed(self, sks, messages, rnd, ctxs=None, key_idx=None, mode=MODE_PURE):
         """PrivateKey::try_sign_with_seed for a batch: rnd = one 32-byte seed per op (zeros =
         deterministic signing).  Raises ValueError if any ctx is longer than 255 bytes
         (src/lib.rs:274).  Returns a uint8 tensor [n_ops, SIG_LEN]."""
+        return self._sign_batch(sks, messages, rnd, ctxs, key_idx,
+                                lambda mb, mo, rn, sg, n, cb, co, ki, st: self.sign_device(sks, mb, mo, rn, sg, n, cb, co, ki, mode, st))
+
+    def _sign_batch(self, sks, messages, rnd, ctxs, key_idx, run):
+        """try_sign_with_seed()'s host side around run(msg_buf, msg_off, rnd, sigs, n_ops, ctx_buf, ctx_off, key_idx, status)"""
         n_ops = len(messages)
         msg_buf, msg_off = _cat_with_offsets(messages, self.device)
         ctx_buf = ctx_off = None
@@ -445,7 +474,7 @@ class MlDsa:
         rnd = self._key_bytes(rnd, 32, "rnd") if n_ops else torch.zeros((1, 32), dtype=torch.uint8, device=self.device)
         sigs = torch.empty((max(n_ops, 1), self.SIG_LEN), dtype=torch.uint8, device=self.device)
         status = torch.zeros(max(n_ops, 1), dtype=torch.int32, device=self.device)
-        self.sign_device(sks, msg_buf, msg_off, rnd, sigs, n_ops, ctx_buf, ctx_off, kidx, mode, status)
+        run(msg_buf, msg_off, rnd, sigs, n_ops, ctx_buf, ctx_off, kidx, status)
         torch.cuda.synchronize(self.device)
         if n_ops and int(status[:n_ops].min()) < 0:
             st = status[:n_ops].cpu().numpy()
@@ -457,9 +486,14 @@ class MlDsa:
             raise ValueError(f"{what} (op {bad})")
         return sigs[:n_ops]
 
-    def try_hash_sign_with_seed(self, sks, messages, rnd, ctxs=None, ph=PH_SHA512, key_idx=None):
+    def try_hash_sign_with_seed(self, sks, messages, rnd, ctxs=None, ph=PH_SHA512, key_idx=None, prehash="host"):
         """PrivateKey::try_hash_sign_with_seed (src/traits.rs:280-284, src/lib.rs:310-342) for a batch: HashML-DSA.Sign
-        with the pre-hash `ph` computed on the host."""
+        with the pre-hash `ph` computed on the host (prehash="host") or on the device (prehash="device", mldsa_hash_sign)."""
+        if _check_prehash(prehash):
+            code = _ph_code(ph)
+            return self._sign_batch(sks, messages, rnd, ctxs, key_idx,
+                                    lambda mb, mo, rn, sg, n, cb, co, ki, st: self.hash_sign_device(sks, mb, mo, rn, sg, n, code, cb, co,
+                                                                                                    ki, st))
         return self.try_sign_with_seed(sks, [hash_message(m, ph) for m in messages], rnd, ctxs=ctxs, key_idx=key_idx,
                                        mode=MODE_PREHASH)
 
@@ -479,6 +513,64 @@ class MlDsa:
             _ptr(msg_buf), _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
             _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
             _ptr(status) if status is not None else null, n_ops, _stream(self.device)))
+        return sigs
+
+    # ---- HashML-DSA with the pre-hash on the device (include/mldsa_ph.h) ------------------
+    def _ph_scratch(self, code, n_ops):
+        """device scratch of one call, from the caching allocator on the current stream (the call uses it in that stream's order)"""
+        nb = _ph_lib.load().mldsa_ph_scratch_bytes(code, n_ops)
+        return torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+
+    @staticmethod
+    def _ph_arg(ph):
+        return ph if isinstance(ph, int) else _ph_code(ph)
+
+    def prehash_device(self, msg_buf, msg_off, n_ops, ph):
+        """mldsa_prehash: rows[n_ops, row_len] = OID || PH(M_i) (= hash_message(M_i, ph)), bad[n_ops] = 1 where the
+        message pair is malformed (row all zero).  Returns (rows, bad); asynchronous on the current stream."""
+        lib, code = _ph_lib.load(), self._ph_arg(ph)
+        rl = lib.mldsa_ph_row_len(code)
+        if rl < 0:
+            raise ValueError(f"unknown ph {ph!r}")
+        rows = torch.empty((max(n_ops, 1), rl), dtype=torch.uint8, device=self.device)
+        bad = torch.empty(max(n_ops, 1), dtype=torch.uint8, device=self.device)
+        _ph_lib.check(lib.mldsa_prehash(self.hp._h, code, _ptr(msg_buf) if msg_buf is not None else C.c_void_p(0), _ptr(msg_off),
+                                        _ptr(rows), _ptr(bad), n_ops, _stream(self.device)))
+        return rows[:n_ops], bad[:n_ops]
+
+    def hash_verify_device(self, pks, msg_buf, msg_off, sigs, ok, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None):
+        """mldsa_hash_verify: verify_device's arguments on RAW messages, the pre-hash `ph` computed on the device."""
+        null, code = C.c_void_p(0), self._ph_arg(ph)
+        scratch = self._ph_scratch(code, n_ops)
+        _ph_lib.check(_ph_lib.load().mldsa_hash_verify(
+            self.hp._h, self.pset, code, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks),
+            _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
+            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null,
+            _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return ok
+
+    def hash_verify_pk_device(self, pk_bytes, msg_buf, msg_off, sigs, ok, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None):
+        """mldsa_hash_verify_pk: verify_pk_device's arguments (wire-format keys) on RAW messages, the pre-hash on the device."""
+        null, code = C.c_void_p(0), self._ph_arg(ph)
+        pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
+        scratch = self._ph_scratch(code, n_ops)
+        _ph_lib.check(_ph_lib.load().mldsa_hash_verify_pk(
+            self.hp._h, self.pset, code, _ptr(pk), pk.shape[0], _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf),
+            _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(sigs),
+            _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return ok
+
+    def hash_sign_device(self, sks, msg_buf, msg_off, rnd, sigs, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None, status=None):
+        """mldsa_hash_sign: sign_device's arguments on RAW messages, the pre-hash `ph` computed on the device.  Synchronous like
+        mldsa_sign: signatures and statuses are final on return."""
+        null, code = C.c_void_p(0), self._ph_arg(ph)
+        scratch = self._ph_scratch(code, n_ops)
+        _ph_lib.check(_ph_lib.load().mldsa_hash_sign(
+            self.hp._h, self.pset, code, _ptr(sks.rho), _ptr(sks.cap_k), _ptr(sks.tr), _ptr(sks.s_1_hat_mont),
+            _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont), len(sks), _ptr(key_idx) if key_idx is not None else null,
+            _ptr(msg_buf), _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
+            _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
+            _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return sigs
 
 

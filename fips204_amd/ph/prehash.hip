@@ -1,0 +1,414 @@
+// HashML-DSA pre-hash on the GPU (include/mldsa_ph.h): PH(M) = SHA-256 / SHA-512 / SHAKE128 of each raw message
+// (reference src/hashing.rs:316-354), then the core's MLDSA_MODE_PREHASH call on the rows OID || PH(M).
+//
+// k_prehash<PH>: one message per lane, 64 per wave (the layout of the core's k_mu).  Each lane absorbs its own blocks
+// and pads its own message; the wave loops to its longest message.  Whole dwords of the message come from one
+// byte-granular dword load each; only the dwords around the message's end are assembled from bytes.  The same launch
+// writes each op's row and the offset table the core call reads (off[i] = i row_len).
+// k_ph_refuse: after the core call, the per-op refusal of ops whose message pair was malformed (the core saw a
+// well-formed table of rows, so it cannot know).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+
+#include "../../include/mldsa_ph.h"
+#include "../csrc/keccak.h"
+#include "sha2_dev.h"
+
+namespace {
+
+using mldsa::KeccakState;
+using mldsa::load_le32;
+using mldsa_ph::bswap32;
+using mldsa_ph::static_for;
+
+constexpr int OID_LEN = 11;
+constexpr uint8_t OID_PREFIX[10] = {0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x02};
+
+template <int PH> struct PhTraits;
+template <> struct PhTraits<MLDSA_PH_SHA256> { static constexpr int BLOCK = 64, TAIL = 9, DIGEST = 32; static constexpr uint8_t OID_LAST = 0x01; };
+template <> struct PhTraits<MLDSA_PH_SHA512> { static constexpr int BLOCK = 128, TAIL = 17, DIGEST = 64; static constexpr uint8_t OID_LAST = 0x03; };
+// SHAKE128: rate 168; the pad (0x1F ... 0x80) always fits in the block that holds the message's end
+template <> struct PhTraits<MLDSA_PH_SHAKE128> { static constexpr int BLOCK = 168, TAIL = 1, DIGEST = 32; static constexpr uint8_t OID_LAST = 0x0b; };
+
+// little-endian dword at byte `pos` of the padded message: message bytes, then PADB, then zeros
+template <uint8_t PADB>
+__device__ __forceinline__ uint32_t padded_le32(const uint8_t* mp, size_t mlen, size_t pos) {
+    if (pos + 4 <= mlen) return load_le32(mp + pos);
+    if (pos > mlen) return 0;
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const size_t p = pos + k;
+        const uint32_t byte = p < mlen ? mp[p] : p == mlen ? PADB : 0u;
+        v |= byte << (8 * k);
+    }
+    return v;
+}
+
+template <int PH>
+__global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off,
+                                                const uint8_t* __restrict__ ctxs, const uint64_t* __restrict__ ctx_off,
+                                                uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
+                                                uint8_t* __restrict__ bad, size_t n_ops) {
+    using T = PhTraits<PH>;
+    constexpr int ROW = OID_LEN + T::DIGEST;
+    const int lane = threadIdx.x;
+    const size_t op = (size_t)blockIdx.x * 64 + lane;
+    const bool valid = op < n_ops;
+
+    // the checks of k_mu: the call vouches for [off[0], off[n_ops]); a pair outside it in order is refused unread
+    const uint8_t* mp = nullptr;
+    size_t mlen = 0;
+    bool msg_bad = false, live = false;
+    if (valid) {
+        const uint64_t m0 = msg_off[op], m1 = msg_off[op + 1];
+        msg_bad = !(msg_off[0] <= m0 && m0 <= m1 && m1 <= msg_off[n_ops]);
+        msg_bad |= m1 != m0 && msgs == nullptr;
+        bool ctx_bad = false;
+        if (ctx_off) {
+            const uint64_t c0 = ctx_off[op], c1 = ctx_off[op + 1];
+            ctx_bad = !(ctx_off[0] <= c0 && c0 <= c1 && c1 <= ctx_off[n_ops]);
+            ctx_bad |= c1 != c0 && ctxs == nullptr;
+            ctx_bad |= !ctx_bad && c1 - c0 > 255;
+        }
+        live = !msg_bad && !ctx_bad;
+        if (live) {
+            mp = msgs + m0;
+            mlen = (size_t)(m1 - m0);
+        }
+    }
+    const size_t my_blocks = live ? (mlen + T::TAIL + T::BLOCK - 1) / T::BLOCK : 0;
+    size_t max_blocks = my_blocks;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const size_t o = (size_t)__shfl_xor((unsigned long long)max_blocks, m);
+        max_blocks = o > max_blocks ? o : max_blocks;
+    }
+
+    uint8_t dig[T::DIGEST];
+    if constexpr (PH == MLDSA_PH_SHA256) {
+        mldsa_ph::Sha256State st;
+        mldsa_ph::sha256_init(st);
+        for (size_t b = 0; b < max_blocks; b++) {
+            if (b < my_blocks) {
+                const size_t base = b * 64;
+                uint32_t w[16];
+                if (base + 64 <= mlen) {
+#pragma unroll
+                    for (int i = 0; i < 16; i++) w[i] = bswap32(load_le32(mp + base + 4 * i));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; i++) w[i] = bswap32(padded_le32<0x80>(mp, mlen, base + 4 * i));
+                    if (b == my_blocks - 1) {  // 64-bit big-endian bit length
+                        w[14] = (uint32_t)(mlen >> 29);
+                        w[15] = (uint32_t)(mlen << 3);
+                    }
+                }
+                mldsa_ph::sha256_block(st, w);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) dig[4 * i + k] = (uint8_t)(st.h[i] >> (24 - 8 * k));
+    } else if constexpr (PH == MLDSA_PH_SHA512) {
+        mldsa_ph::Sha512State st;
+        mldsa_ph::sha512_init(st);
+        for (size_t b = 0; b < max_blocks; b++) {
+            if (b < my_blocks) {
+                const size_t base = b * 128;
+                mldsa_ph::U64 w[16];
+                if (base + 128 <= mlen) {
+#pragma unroll
+                    for (int i = 0; i < 16; i++) {
+                        w[i].hi = bswap32(load_le32(mp + base + 8 * i));
+                        w[i].lo = bswap32(load_le32(mp + base + 8 * i + 4));
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; i++) {
+                        w[i].hi = bswap32(padded_le32<0x80>(mp, mlen, base + 8 * i));
+                        w[i].lo = bswap32(padded_le32<0x80>(mp, mlen, base + 8 * i + 4));
+                    }
+                    if (b == my_blocks - 1) {  // 128-bit big-endian bit length, high half 0
+                        w[14] = {0u, 0u};
+                        w[15] = {(uint32_t)(mlen << 3), (uint32_t)(mlen >> 29)};
+                    }
+                }
+                mldsa_ph::sha512_block(st, w);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                dig[8 * i + k] = (uint8_t)(st.h[i].hi >> (24 - 8 * k));
+                dig[8 * i + 4 + k] = (uint8_t)(st.h[i].lo >> (24 - 8 * k));
+            }
+    } else {
+        KeccakState st;
+        mldsa::keccak_zero(st);
+        for (size_t b = 0; b < max_blocks; b++) {
+            if (b < my_blocks) {
+                const size_t base = b * 168;
+                if (base + 168 <= mlen) {
+                    static_for<0, 21>([&](auto wc) {
+                        constexpr int W = decltype(wc)::value;
+                        st.lo[W] ^= load_le32(mp + base + 8 * W);
+                        st.hi[W] ^= load_le32(mp + base + 8 * W + 4);
+                    });
+                } else {
+                    static_for<0, 21>([&](auto wc) {
+                        constexpr int W = decltype(wc)::value;
+                        st.lo[W] ^= padded_le32<0x1F>(mp, mlen, base + 8 * W);
+                        st.hi[W] ^= padded_le32<0x1F>(mp, mlen, base + 8 * W + 4);
+                    });
+                }
+                if (b == my_blocks - 1) st.hi[20] ^= 0x80000000u;  // last byte of the rate block
+                mldsa::keccak_f1600(st);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                dig[8 * i + k] = (uint8_t)(st.lo[i] >> (8 * k));
+                dig[8 * i + 4 + k] = (uint8_t)(st.hi[i] >> (8 * k));
+            }
+    }
+
+    if (valid) {
+        uint8_t* row = out + op * ROW;
+#pragma unroll
+        for (int i = 0; i < 10; i++) row[i] = live ? OID_PREFIX[i] : 0;
+        row[10] = live ? T::OID_LAST : 0;
+#pragma unroll
+        for (int i = 0; i < T::DIGEST; i++) row[OID_LEN + i] = live ? dig[i] : 0;
+        if (bad) bad[op] = msg_bad ? 1 : 0;
+        if (out_off) {
+            out_off[op] = (uint64_t)op * ROW;
+            if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * ROW;
+        }
+    }
+}
+
+// ops whose message pair was malformed: ok = 0, status MLDSA_ERR_PARAM, an all-zero signature
+__global__ __launch_bounds__(64) void k_ph_refuse(const uint8_t* __restrict__ bad, uint8_t* __restrict__ ok,
+                                                  uint8_t* __restrict__ sigs, size_t sig_len, int32_t* __restrict__ status,
+                                                  size_t n_ops) {
+    const int lane = threadIdx.x;
+    const size_t op0 = (size_t)blockIdx.x * 64;
+    const size_t op = op0 + lane;
+    const bool b = op < n_ops && bad[op] != 0;
+    if (b) {
+        if (ok) ok[op] = 0;
+        if (status) status[op] = MLDSA_ERR_PARAM;
+    }
+    if (!sigs) return;
+    uint64_t mask = __ballot(b);
+    while (mask) {  // the wave clears the refused signatures one by one, consecutive lanes on consecutive bytes
+        const int l = __ffsll((unsigned long long)mask) - 1;
+        mask &= mask - 1;
+        uint8_t* row = sigs + (op0 + l) * sig_len;
+        for (size_t i = lane; i < sig_len; i += 64) row[i] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+thread_local std::string g_err;
+
+int fail(int rc, const std::string& msg) {
+    g_err = msg;
+    return rc;
+}
+
+int row_len_of(int ph) {
+    switch (ph) {
+        case MLDSA_PH_SHA256: return OID_LEN + 32;
+        case MLDSA_PH_SHA512: return OID_LEN + 64;
+        case MLDSA_PH_SHAKE128: return OID_LEN + 32;
+        default: return -1;
+    }
+}
+
+// scratch = [offset table: 8 (n + 1)] [rows: n row_len] [bad: n]; 0 when it does not fit a size_t
+size_t scratch_of(int ph, size_t n) {
+    const int rl = row_len_of(ph);
+    if (rl < 0) return 0;
+    const size_t lim = ~(size_t)0 / 128;
+    if (n >= lim) return 0;
+    return 8 * (n + 1) + n * (size_t)rl + n;
+}
+
+// the context's device for the call, the caller's current device afterwards
+struct DeviceScope {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceScope(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+int launch_prehash(int ph, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off, uint8_t* out,
+                   uint64_t* out_off, uint8_t* bad, size_t n_ops, hipStream_t s) {
+    const dim3 grid((unsigned)((n_ops + 63) / 64)), block(64);
+    switch (ph) {
+        case MLDSA_PH_SHA256:
+            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHA256>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
+            break;
+        case MLDSA_PH_SHA512:
+            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHA512>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
+            break;
+        default:
+            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHAKE128>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
+            break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MLDSA_ERR_DEVICE, std::string("k_prehash launch: ") + hipGetErrorString(e));
+    return MLDSA_OK;
+}
+
+int launch_refuse(const uint8_t* bad, uint8_t* ok, uint8_t* sigs, size_t sig_len, int32_t* status, size_t n_ops, hipStream_t s) {
+    hipLaunchKernelGGL(k_ph_refuse, dim3((unsigned)((n_ops + 63) / 64)), dim3(64), 0, s, bad, ok, sigs, sig_len, status, n_ops);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MLDSA_ERR_DEVICE, std::string("k_ph_refuse launch: ") + hipGetErrorString(e));
+    return MLDSA_OK;
+}
+
+int core_failed(const char* fn, int rc) {
+    const char* m = mldsa_last_error();
+    return fail(rc, std::string(fn) + ": " + (m ? m : "(no message)"));
+}
+
+// the checks shared by the op-level calls, all before anything is launched
+struct Scratch {
+    uint64_t* off;
+    uint8_t* rows;
+    uint8_t* bad;
+};
+
+int check_call(const char* fn, mldsa_ctx* ctx, int set, int ph, size_t n_keys, const uint32_t* key_idx, size_t n_ops, void* scratch,
+               size_t scratch_bytes, mldsa_params* p, Scratch* sc) {
+    const int rl = row_len_of(ph);
+    if (rl < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown ph");
+    if (!ctx) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL context");
+    if (mldsa_get_params(set, p) != MLDSA_OK) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown parameter set");
+    if (key_idx ? n_keys == 0 : n_keys < n_ops) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": n_keys does not cover the batch");
+    const size_t need = scratch_of(ph, n_ops);
+    if (!scratch || need == 0 || scratch_bytes < need || ((uintptr_t)scratch & 7) != 0)
+        return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL, misaligned or smaller than mldsa_ph_scratch_bytes");
+    uint8_t* base = static_cast<uint8_t*>(scratch);
+    sc->off = reinterpret_cast<uint64_t*>(base);
+    sc->rows = base + 8 * (n_ops + 1);
+    sc->bad = sc->rows + n_ops * (size_t)rl;
+    return MLDSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mldsa_ph_abi_version(void) { return MLDSA_PH_ABI_VERSION; }
+
+const char* mldsa_ph_last_error(void) { return g_err.c_str(); }
+
+int mldsa_ph_row_len(int ph) { return row_len_of(ph); }
+
+size_t mldsa_ph_scratch_bytes(int ph, size_t n_ops) { return scratch_of(ph, n_ops); }
+
+int mldsa_prehash(mldsa_ctx* ctx, int ph, const uint8_t* msgs, const uint64_t* msg_off, uint8_t* out, uint8_t* bad, size_t n_ops,
+                  void* stream) {
+    if (row_len_of(ph) < 0) return fail(MLDSA_ERR_PARAM, "mldsa_prehash: unknown ph");
+    if (n_ops == 0) return MLDSA_OK;
+    if (!ctx || !msg_off || !out) return fail(MLDSA_ERR_PARAM, "mldsa_prehash: NULL pointer");
+    const int dev = mldsa_ctx_device(ctx);
+    if (dev < 0) return fail(MLDSA_ERR_PARAM, "mldsa_prehash: bad context");
+    DeviceScope ds(dev);
+    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, "mldsa_prehash: hipSetDevice failed");
+    return launch_prehash(ph, msgs, msg_off, nullptr, nullptr, out, nullptr, bad, n_ops, (hipStream_t)stream);
+}
+
+int mldsa_hash_verify(mldsa_ctx* ctx, int set, int ph, const uint8_t* rho, const uint8_t* tr, const int32_t* t1_d2_hat_mont,
+                      size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs,
+                      const uint64_t* ctx_off, const uint8_t* sigs, uint8_t* ok, size_t n_ops, void* scratch, size_t scratch_bytes,
+                      void* stream) {
+    if (row_len_of(ph) < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify: unknown ph");
+    if (n_ops == 0) return MLDSA_OK;
+    if (!rho || !tr || !t1_d2_hat_mont || !msg_off || !sigs || !ok) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify: NULL pointer");
+    mldsa_params p;
+    Scratch sc;
+    int rc = check_call("mldsa_hash_verify", ctx, set, ph, n_keys, key_idx, n_ops, scratch, scratch_bytes, &p, &sc);
+    if (rc != MLDSA_OK) return rc;
+    const int dev = mldsa_ctx_device(ctx);
+    if (dev < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify: bad context");
+    DeviceScope ds(dev);
+    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, "mldsa_hash_verify: hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    rc = launch_prehash(ph, msgs, msg_off, ctxs, ctx_off, sc.rows, sc.off, sc.bad, n_ops, s);
+    if (rc != MLDSA_OK) return rc;
+    rc = mldsa_verify(ctx, set, MLDSA_MODE_PREHASH, rho, tr, t1_d2_hat_mont, n_keys, key_idx, sc.rows, sc.off, ctxs, ctx_off, sigs, ok,
+                      n_ops, stream);
+    if (rc != MLDSA_OK) return core_failed("mldsa_hash_verify", rc);
+    return launch_refuse(sc.bad, ok, nullptr, 0, nullptr, n_ops, s);
+}
+
+int mldsa_hash_verify_pk(mldsa_ctx* ctx, int set, int ph, const uint8_t* pk, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
+                         const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off, const uint8_t* sigs, uint8_t* ok,
+                         size_t n_ops, void* scratch, size_t scratch_bytes, void* stream) {
+    if (row_len_of(ph) < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify_pk: unknown ph");
+    if (n_ops == 0) return MLDSA_OK;
+    if (!pk || !msg_off || !sigs || !ok) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify_pk: NULL pointer");
+    mldsa_params p;
+    Scratch sc;
+    int rc = check_call("mldsa_hash_verify_pk", ctx, set, ph, n_keys, key_idx, n_ops, scratch, scratch_bytes, &p, &sc);
+    if (rc != MLDSA_OK) return rc;
+    const int dev = mldsa_ctx_device(ctx);
+    if (dev < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_verify_pk: bad context");
+    DeviceScope ds(dev);
+    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, "mldsa_hash_verify_pk: hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    rc = launch_prehash(ph, msgs, msg_off, ctxs, ctx_off, sc.rows, sc.off, sc.bad, n_ops, s);
+    if (rc != MLDSA_OK) return rc;
+    rc = mldsa_verify_pk(ctx, set, MLDSA_MODE_PREHASH, pk, n_keys, key_idx, sc.rows, sc.off, ctxs, ctx_off, sigs, ok, n_ops, stream);
+    if (rc != MLDSA_OK) return core_failed("mldsa_hash_verify_pk", rc);
+    return launch_refuse(sc.bad, ok, nullptr, 0, nullptr, n_ops, s);
+}
+
+int mldsa_hash_sign(mldsa_ctx* ctx, int set, int ph, const uint8_t* rho, const uint8_t* cap_k, const uint8_t* tr,
+                    const int32_t* s_1_hat_mont, const int32_t* s_2_hat_mont, const int32_t* t_0_hat_mont, size_t n_keys,
+                    const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off,
+                    const uint8_t* rnd, uint8_t* sigs, int32_t* status, size_t n_ops, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+    if (row_len_of(ph) < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_sign: unknown ph");
+    if (n_ops == 0) return MLDSA_OK;
+    if (!rho || !cap_k || !tr || !s_1_hat_mont || !s_2_hat_mont || !t_0_hat_mont || !msg_off || !rnd || !sigs)
+        return fail(MLDSA_ERR_PARAM, "mldsa_hash_sign: NULL pointer");
+    mldsa_params p;
+    Scratch sc;
+    int rc = check_call("mldsa_hash_sign", ctx, set, ph, n_keys, key_idx, n_ops, scratch, scratch_bytes, &p, &sc);
+    if (rc != MLDSA_OK) return rc;
+    const int dev = mldsa_ctx_device(ctx);
+    if (dev < 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_sign: bad context");
+    DeviceScope ds(dev);
+    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, "mldsa_hash_sign: hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    rc = launch_prehash(ph, msgs, msg_off, ctxs, ctx_off, sc.rows, sc.off, sc.bad, n_ops, s);
+    if (rc != MLDSA_OK) return rc;
+    rc = mldsa_sign(ctx, set, MLDSA_MODE_PREHASH, rho, cap_k, tr, s_1_hat_mont, s_2_hat_mont, t_0_hat_mont, n_keys, key_idx, sc.rows,
+                    sc.off, ctxs, ctx_off, rnd, sigs, status, n_ops, stream);
+    if (rc != MLDSA_OK) return core_failed("mldsa_hash_sign", rc);
+    rc = launch_refuse(sc.bad, nullptr, sigs, (size_t)p.sig_len, status, n_ops, s);
+    if (rc != MLDSA_OK) return rc;
+    const hipError_t e = hipStreamSynchronize(s);  // synchronous like mldsa_sign: statuses and signatures are final
+    if (e != hipSuccess) return fail(MLDSA_ERR_DEVICE, std::string("mldsa_hash_sign: ") + hipGetErrorString(e));
+    return MLDSA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,78 @@
+/* mldsa_ph.h -- HashML-DSA with the pre-hash on the GPU (libmldsa_ph.so).
+ *
+ * A front-end library layered on the C ABI of include/mldsa_hip.h.  It computes PH(M) -- SHA-256, SHA-512 or
+ * SHAKE128 of each raw message, the reference's hash_message (src/hashing.rs:316-354) -- in one kernel, one
+ * message per lane, writes OID || PH(M) for every operation into caller-provided device scratch, and then calls
+ * mldsa_verify / mldsa_verify_pk / mldsa_sign with MLDSA_MODE_PREHASH on the same stream.  It reaches the core
+ * only through the core's public entry points, so every core call's behaviour is the core's.
+ *
+ * Conventions are those of mldsa_hip.h: pointers to operation data are device pointers, `stream` is a
+ * hipStream_t (NULL = the default stream), calls return MLDSA_OK or a negative MLDSA_ERR_* and never abort.
+ *
+ * Argument errors: an unknown `ph`, a NULL pointer the call needs while n_ops > 0, or `scratch` that is NULL,
+ *   not 8-byte aligned or smaller than mldsa_ph_scratch_bytes(ph, n_ops) return MLDSA_ERR_PARAM before anything
+ *   is launched.  n_ops = 0 returns MLDSA_OK.  Errors of the core call pass through with their code, and
+ *   mldsa_ph_last_error() then carries the core's message.
+ * Offsets are untrusted, with the rule of mldsa_verify: an op whose message pair is not in order inside
+ *   [msg_off[0], msg_off[n_ops]], or that names bytes of a NULL `msgs`, is refused on its own -- ok = 0, status
+ *   MLDSA_ERR_PARAM and an all-zero signature -- and no byte of its message is read.  An op whose ctx pair is
+ *   malformed or whose ctx is longer than 255 bytes is not hashed either (no byte of its message is read) and
+ *   gets the core's result: ok = 0 / MLDSA_ERR_CTX_LEN (lib.rs:274, 368).  A malformed message pair takes
+ *   precedence over |ctx| > 255, as in the core.  Other ops are unaffected.
+ * Device and stream: every call launches on mldsa_ctx_device(ctx) and restores the caller's current device.
+ *   mldsa_prehash and the verify calls are asynchronous on `stream` and never synchronise the host;
+ *   mldsa_hash_sign is synchronous like mldsa_sign: signatures and statuses are final when it returns.
+ *   Scratch is used in stream order on `stream`: it may be reused by the next call on the same stream.
+ */
+#ifndef MLDSA_PH_H
+#define MLDSA_PH_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mldsa_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MLDSA_PH_ABI_VERSION 1
+#define MLDSA_PH_SHA256 0   /* OID 2.16.840.1.101.3.4.2.1,  32-byte digest (hashing.rs:319-329) */
+#define MLDSA_PH_SHA512 1   /* OID 2.16.840.1.101.3.4.2.3,  64-byte digest (hashing.rs:330-340) */
+#define MLDSA_PH_SHAKE128 2 /* OID 2.16.840.1.101.3.4.2.11, 32 bytes of output (hashing.rs:341-352) */
+
+int mldsa_ph_abi_version(void);
+/* message of the last failed call of this thread; carries the core's message when a core call failed */
+const char *mldsa_ph_last_error(void);
+/* 43 / 75 / 43 = 11-byte DER OID + digest; negative for an unknown ph */
+int mldsa_ph_row_len(int ph);
+/* device scratch the op-level calls need for n_ops operations: 8 (n_ops + 1) + n_ops row_len + n_ops bytes;
+ * 0 for an unknown ph (or a size that does not fit a size_t) */
+size_t mldsa_ph_scratch_bytes(int ph, size_t n_ops);
+
+/* The seam: out[n_ops][row_len] = OID || PH(M_i) for the messages msgs[msg_off[i], msg_off[i + 1]).  An op with a
+ * malformed pair gets an all-zero row and bad[i] = 1 (else bad[i] = 0); bad may be NULL.  Asynchronous on stream. */
+int mldsa_prehash(mldsa_ctx *ctx, int ph, const uint8_t *msgs, const uint64_t *msg_off, uint8_t *out, uint8_t *bad,
+                  size_t n_ops, void *stream);
+
+/* HashML-DSA.Verify / .Sign (src/lib.rs:391-411, 310-342) on RAW messages: arguments, refusal rules and results are
+ * those of mldsa_verify / mldsa_verify_pk / mldsa_sign with mode = MLDSA_MODE_PREHASH and msg_i = OID || PH(M_i),
+ * plus ph and a caller-owned device scratch of >= mldsa_ph_scratch_bytes(ph, n_ops) bytes. */
+int mldsa_hash_verify(mldsa_ctx *ctx, int set, int ph, const uint8_t *rho, const uint8_t *tr, const int32_t *t1_d2_hat_mont,
+                      size_t n_keys, const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off,
+                      const uint8_t *ctxs, const uint64_t *ctx_off, const uint8_t *sigs, uint8_t *ok, size_t n_ops,
+                      void *scratch, size_t scratch_bytes, void *stream);
+int mldsa_hash_verify_pk(mldsa_ctx *ctx, int set, int ph, const uint8_t *pk, size_t n_keys, const uint32_t *key_idx,
+                         const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *ctxs, const uint64_t *ctx_off,
+                         const uint8_t *sigs, uint8_t *ok, size_t n_ops, void *scratch, size_t scratch_bytes, void *stream);
+int mldsa_hash_sign(mldsa_ctx *ctx, int set, int ph, const uint8_t *rho, const uint8_t *cap_k, const uint8_t *tr,
+                    const int32_t *s_1_hat_mont, const int32_t *s_2_hat_mont, const int32_t *t_0_hat_mont, size_t n_keys,
+                    const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *ctxs,
+                    const uint64_t *ctx_off, const uint8_t *rnd, uint8_t *sigs, int32_t *status, size_t n_ops,
+                    void *scratch, size_t scratch_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MLDSA_PH_H */

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""HashML-DSA with the pre-hash on the device (include/mldsa_ph.h) against the host pre-hash, ML-DSA-65: one JSON line per
+(message length, PH) point.
+
+Per point: mldsa_prehash alone (us, GB/s of message, fraction of the derived issue ceiling), hash_verify_device and
+hash_sign_device (ms), the same calls with the host pre-hash (hashlib loop included), and pure-mode verify_device /
+sign_device on the same raw messages (one lane-per-message pass over the bytes in k_mu).  Device times are hipEvent times
+after warm-up; host-path times are wall clock around the whole list-level call.
+
+The ceiling: cycles per block per wave = sum over the kernel's instruction classes of count x issue cost.  The counts are
+those of k_prehash<PH>'s compression loop in its disassembly (llvm-objdump -d --mcpu=gfx950 of the device object of
+fips204_amd/ph/prehash.hip); the issue costs are the column cyc/instr@clk of tools/ubench_valu.hip's output (--ubench FILE).
+Ceiling GB/s = SIMDs x clock x 64 lanes x block bytes / cycles per block, for one message per lane and full issue.
+
+    python tools/bench_prehash.py --ubench profiles/prehash_ubench_valu.txt > profiles/prehash_bench.jsonl
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SIMDS, CLOCK_GHZ = 256 * 4, 2.4
+BLOCK_BYTES = {"SHA256": 64, "SHA512": 128, "SHAKE128": 168}
+# instruction classes of one block of one wave, from the disassembly of k_prehash<PH> (counts of the compression / permutation loop)
+MIX = {
+    "SHA256": {"v_alignbit_b32": 576, "v_bitop3_b32": 352, "v_add3_u32": 241, "v_add_u32": 119, "v_lshrrev_b32": 96, "v_perm_b32": 16},
+    "SHA512": {"v_alignbit_b32": 1570, "v_bitop3_b32": 896, "v_lshl_add_u64": 768, "v_add3_u32": 448, "v_mov_b32": 992,
+               "v_add_u32": 247, "v_lshrrev_b32": 128, "v_perm_b32": 32},
+    # 24 rounds of csrc/keccak.h (70 bitop3 + 58 alignbit + 62 xor per round) + the 42 absorbing XORs
+    "SHAKE128": {"v_bitop3_b32": 24 * 70, "v_alignbit_b32": 24 * 58, "v_xor_b32": 24 * 62 + 42},
+}
+
+
+def issue_costs(path):
+    """instruction -> cycles per wave64 instruction (cyc/instr@clk) from a ubench_valu output file"""
+    costs = {}
+    for ln in open(path):
+        parts = ln.split()
+        if len(parts) == 6 and parts[0].startswith("v_"):
+            try:
+                costs[parts[0]] = float(parts[5])
+            except ValueError:
+                pass
+    return costs
+
+
+def ceiling(ph, costs):
+    mix = MIX[ph]
+    missing = sorted(k for k in mix if k not in costs)
+    if missing:
+        return None, {"missing_issue_costs": missing}
+    cyc = sum(n * costs[k] for k, n in mix.items())
+    gbs = SIMDS * CLOCK_GHZ * 64 * BLOCK_BYTES[ph] / cyc
+    return gbs, {"mix_per_block_per_wave": mix, "cycles_per_block_per_wave": round(cyc, 1), "ceiling_GBs": round(gbs, 1),
+                 "formula": "simds * clock_GHz * 64 lanes * block_bytes / cycles_per_block"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=65536)
+    ap.add_argument("--lens", default="64,1024,16384")
+    ap.add_argument("--phs", default="SHA256,SHA512,SHAKE128")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--big", type=int, default=262144, help="also the 1 KiB point at this many ops (0: skip)")
+    ap.add_argument("--ubench", default=os.path.join(ROOT, "profiles", "prehash_ubench_valu.txt"))
+    ap.add_argument("--no-host", action="store_true", help="skip the host pre-hash calls")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    from fips204_amd.ml_dsa import MODE_PREHASH, MlDsa, hash_message
+
+    costs = issue_costs(args.ubench) if os.path.exists(args.ubench) else {}
+    m = MlDsa(65)
+    nk = 64
+    pk, sk = m.keygen_from_seed([bytes([i]) * 32 for i in range(nk)])
+    pks, sks = m.public_keys_from_bytes(pk), m.private_keys_from_bytes(sk)
+
+    def timed(fn, steps, warmup):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / steps  # ms
+
+    points = [(n_, L, ph) for L in [int(x) for x in args.lens.split(",")] for ph in args.phs.split(",") for n_ in [args.n]]
+    if args.big:
+        points += [(args.big, 1024, ph) for ph in args.phs.split(",")]
+    for n, L, ph in points:
+        g = torch.Generator(device="cuda").manual_seed(L)
+        buf = torch.randint(0, 256, (n * L + 16,), dtype=torch.uint8, device="cuda", generator=g)
+        off = torch.arange(n + 1, dtype=torch.int64, device="cuda") * L
+        kidx = torch.from_numpy((np.arange(n) % nk).astype(np.int32)).cuda()
+        rnd = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+        sigs = torch.empty((n, m.SIG_LEN), dtype=torch.uint8, device="cuda")
+        ok = torch.empty(n, dtype=torch.uint8, device="cuda")
+        st = torch.empty(n, dtype=torch.int32, device="cuda")
+        ph_ms = timed(lambda: m.prehash_device(buf, off, n, ph), args.steps, args.warmup)
+        hs_ms = timed(lambda: m.hash_sign_device(sks, buf, off, rnd, sigs, n, ph, key_idx=kidx, status=st), max(2, args.steps // 3), 1)
+        assert int(st.min()) == 0
+        hv_ms = timed(lambda: m.hash_verify_device(pks, buf, off, sigs, ok, n, ph, key_idx=kidx), args.steps, args.warmup)
+        assert bool(ok.all())
+        pv_ms = timed(lambda: m.verify_device(pks, buf, off, sigs, ok, n, key_idx=kidx), args.steps, args.warmup)
+        ps_ms = timed(lambda: m.sign_device(sks, buf, off, rnd, sigs, n, key_idx=kidx, status=st), max(2, args.steps // 3), 1)
+        gbs = n * L / (ph_ms * 1e-3) / 1e9
+        ceil_gbs, ceil = ceiling(ph, costs) if costs else (None, {"missing_issue_costs": "no ubench file"})
+        rec = {"workload": "prehash", "set": 65, "ph": ph, "n_ops": n, "msg_len": L,
+               "prehash_us": round(ph_ms * 1e3, 1), "prehash_GBs": round(gbs, 1),
+               "prehash_fraction_of_ceiling": round(gbs / ceil_gbs, 3) if ceil_gbs else None,
+               "hash_verify_device_ms": round(hv_ms, 3), "hash_sign_device_ms": round(hs_ms, 3),
+               "pure_verify_device_ms": round(pv_ms, 3), "pure_sign_device_ms": round(ps_ms, 3), "ceiling": ceil}
+        if not args.no_host and n == args.n:
+            raw = buf[:n * L].cpu().numpy().tobytes()
+            msgs = [raw[i * L:(i + 1) * L] for i in range(n)]
+            kh = np.arange(n, dtype=np.uint32) % nk
+            sig_t = sigs.clone()
+            t0 = time.perf_counter()
+            m.verify(pks, [hash_message(x, ph) for x in msgs], sig_t, key_idx=kh, mode=MODE_PREHASH)
+            rec["hash_verify_host_prehash_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            t0 = time.perf_counter()
+            m.try_sign_with_seed(sks, [hash_message(x, ph) for x in msgs], rnd, key_idx=kh, mode=MODE_PREHASH)
+            rec["hash_sign_host_prehash_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            t0 = time.perf_counter()
+            [hash_message(x, ph) for x in msgs]
+            rec["host_prehash_loop_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            del msgs, raw
+        print(json.dumps(rec), flush=True)
+        del buf, sigs
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -53,8 +53,30 @@ DEFINE_KERNEL(k_cndmask, "v_cndmask_b32 %0, %0, %1, vcc")
 DEFINE_KERNEL(k_dpp_mov, "v_mov_b32_dpp %0, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
 DEFINE_KERNEL(k_dpp_add, "v_add_u32_dpp %0, %1, %0 row_ror:8 row_mask:0xf bank_mask:0xf")
 DEFINE_KERNEL(k_permlane32, "s_nop 1\n\tv_permlane32_swap_b32 %0, %1")
+// the pre-hash kernels' mix (fips204_amd/ph): three-input add, byte permute, 64-bit add, three-input logic, shift
+DEFINE_KERNEL(k_add3, "v_add3_u32 %0, %0, %1, %2")
+DEFINE_KERNEL(k_perm, "v_perm_b32 %0, %0, %1, %2")
+DEFINE_KERNEL(k_bitop3, "v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96")
+DEFINE_KERNEL(k_lshr, "v_lshrrev_b32 %0, 3, %0")
+DEFINE_KERNEL(k_mov, "v_mov_b32 %0, %1")
 DEFINE_KERNEL(k_bpermute, "ds_bpermute_b32 %0, %1, %0\n\ts_waitcnt lgkmcnt(0)")
 DEFINE_KERNEL(k_swizzle, "ds_swizzle_b32 %0, %0 offset:swizzle(BITMASK_PERM,\"0000p\")\n\ts_waitcnt lgkmcnt(0)")
+
+// 64-bit add as the compiler emits it for SHA-512's uint64_t sums on gfx950 (v_lshl_add_u64 with shift 0)
+__global__ __launch_bounds__(256) void k_add64(uint32_t* out, int iters) {
+    CLK_BEGIN
+    uint64_t a[ILP];
+    const uint64_t b = threadIdx.x * 2654435761ull + 12345u;
+    for (int j = 0; j < ILP; j++) a[j] = threadIdx.x + j * 977u + 1u;
+    for (int i = 0; i < iters; i++) {
+#pragma unroll
+        for (int j = 0; j < ILP; j++) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(a[j]) : "v"(b));
+    }
+    uint32_t s = 0;
+    for (int j = 0; j < ILP; j++) s += (uint32_t)a[j] + (uint32_t)(a[j] >> 32);
+    out[blockIdx.x * 256 + threadIdx.x] = s;
+    CLK_END
+}
 
 // 64-bit multiply-add (one instruction produces a 64-bit result)
 __global__ __launch_bounds__(256) void k_mad_u64(uint32_t* out, int iters) {
@@ -108,6 +130,7 @@ int main() {
         {"v_and_or_b32", k_and_or}, {"v_cndmask_b32", k_cndmask}, {"v_mad_u64_u32", k_mad_u64},
         {"v_mov_b32_dpp", k_dpp_mov}, {"v_add_u32_dpp", k_dpp_add}, {"v_permlane32_swap(+s_nop1)", k_permlane32},
         {"ds_bpermute_b32(+wait)", k_bpermute}, {"ds_swizzle_b32(+wait)", k_swizzle},
+        {"v_add3_u32", k_add3}, {"v_perm_b32", k_perm}, {"v_bitop3_b32", k_bitop3}, {"v_lshrrev_b32", k_lshr}, {"v_lshl_add_u64", k_add64}, {"v_mov_b32", k_mov},
     };
     printf("device: %s, %d CUs, clock %d MHz\n", prop.name, n_cu, prop.clockRate / 1000);
     printf("%-28s %12s %16s %18s %10s %14s\n", "instruction", "ms", "Glane-ops/s", "cyc/instr@2.4GHz", "clock MHz", "cyc/instr@clk");
