@@ -33,8 +33,24 @@ _SIGNATURES = {
     # ctx, set, ph, rho, K, tr, s1, s2, t0, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, rnd, sigs, status, n_ops, scratch,
     # scratch_bytes, stream
     "mldsa_hash_sign": [_P, _I, _I] + [_P] * 6 + [_SZ] + [_P] * 8 + [_SZ, _P, _SZ, _P],
+    # the incremental pre-hash
+    "mldsa_ph_state_bytes": [_I, _SZ],
+    # ctx, ph, state, state_bytes, n_ops, stream
+    "mldsa_ph_init": [_P, _I, _P, _SZ, _SZ, _P],
+    # ctx, ph, state, state_bytes, pieces, piece_off, n_ops, stream
+    "mldsa_ph_update": [_P, _I, _P, _SZ, _P, _P, _SZ, _P],
+    # ctx, ph, state, state_bytes, out, out_off, bad, n_ops, stream
+    "mldsa_ph_final": [_P, _I, _P, _SZ, _P, _P, _P, _SZ, _P],
+    # HashML-DSA from host memory: ctx, staging_bytes, out
+    "mldsa_ph_host_create": [_P, _SZ, C.POINTER(_P)],
+    "mldsa_ph_host_destroy": [_P],
+    # h, set, ph, pk, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, sigs, ok, n_ops
+    "mldsa_hash_verify_host": [_P, _I, _I, _P, _SZ] + [_P] * 7 + [_SZ],
+    # h, set, ph, sk, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, rnd, sigs, status, n_ops
+    "mldsa_hash_sign_host": [_P, _I, _I, _P, _SZ] + [_P] * 8 + [_SZ],
 }
-_RESTYPES = {"mldsa_ph_last_error": C.c_char_p, "mldsa_ph_scratch_bytes": _SZ}
+_RESTYPES = {"mldsa_ph_last_error": C.c_char_p, "mldsa_ph_scratch_bytes": _SZ, "mldsa_ph_state_bytes": _SZ,
+             "mldsa_ph_host_destroy": None}
 
 _lib_ph = None
 

@@ -574,6 +574,118 @@ class MlDsa:
         return sigs
 
 
+    # ---- incremental pre-hash and HashML-DSA from host memory (include/mldsa_ph.h) -------------
+    def prehash_stream(self, n_ops, ph):
+        """mldsa_ph_init: fresh hash states for n_ops messages that arrive in pieces.  Returns a PrehashStream:
+        update(piece_buf, piece_off) any number of times, then final() -> (rows, bad) as prehash_device gives them."""
+        return PrehashStream(self, n_ops, ph)
+
+    def _ph_host(self, staging_bytes):
+        """the mldsa_ph_host of this staging size on this context (created on first use, kept)"""
+        hosts = self.__dict__.setdefault("_ph_hosts", {})
+        h = hosts.get(staging_bytes)
+        if h is None:
+            h = _PhHost(self.hp, staging_bytes)
+            hosts[staging_bytes] = h
+        return h.handle
+
+    def hash_verify_host(self, pk_bytes, messages, sigs, ctxs=None, ph=PH_SHA512, key_idx=None, out=None, staging_bytes=0):
+        """mldsa_hash_verify_host: verify_host's arguments on RAW messages in host memory; the pre-hash `ph` is computed on the
+        device while the message bytes stream through two staging chunks of `staging_bytes` (0 = the library's default)."""
+        code = self._ph_arg(ph)
+        pk = self._np_u8(pk_bytes, self.PK_LEN, "pk")
+        sg = self._np_u8(sigs, self.SIG_LEN, "sigs")
+        n_keys, n_ops = pk.size // self.PK_LEN, sg.size // self.SIG_LEN
+        mflat, moff = self._host_strings(messages, n_ops, "messages")
+        cflat = coff = None
+        if ctxs is not None:
+            cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
+        kidx = _check_key_idx(key_idx, n_keys, n_ops)
+        ok = self._host_out(out, np.uint8, n_ops, "hash_verify_host: out") if out is not None else np.zeros(max(n_ops, 1), dtype=np.uint8)
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
+        _ph_lib.check(_ph_lib.load().mldsa_hash_verify_host(self._ph_host(staging_bytes), self.pset, code, vp(pk), n_keys, vp(kidx),
+                                                            vp(mflat), vp(moff), vp(cflat), vp(coff), vp(sg), vp(ok), n_ops))
+        return ok[:n_ops].astype(bool)
+
+    def hash_sign_host(self, sk_bytes, messages, rnd, ctxs=None, ph=PH_SHA512, key_idx=None, out=None, staging_bytes=0):
+        """mldsa_hash_sign_host: sign_host's arguments on RAW messages in host memory, the pre-hash `ph` on the device;
+        returns uint8 [n_ops, SIG_LEN].  out: (sig uint8[n_ops, SIG_LEN], status int32[n_ops]) buffers of the caller."""
+        code = self._ph_arg(ph)
+        sk = self._np_u8(sk_bytes, self.SK_LEN, "sk")
+        rn = self._np_u8(rnd, 32, "rnd")
+        n_keys, n_ops = sk.size // self.SK_LEN, rn.size // 32
+        mflat, moff = self._host_strings(messages, n_ops, "messages")
+        cflat = coff = None
+        if ctxs is not None:
+            cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
+        kidx = _check_key_idx(key_idx, n_keys, n_ops)
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 2:
+                raise ValueError("hash_sign_host: out = (sig uint8[n_ops, SIG_LEN], status int32[n_ops])")
+            sig = self._host_out(out[0], np.uint8, n_ops * self.SIG_LEN, "hash_sign_host: out[0] (signatures)")
+            status = self._host_out(out[1], np.int32, n_ops, "hash_sign_host: out[1] (status)")
+            if sig.ndim == 2 and sig.shape[1] != self.SIG_LEN:
+                raise ValueError(f"hash_sign_host: out[0] rows must be SIG_LEN = {self.SIG_LEN} bytes")
+            sig = sig.reshape(-1)[:n_ops * self.SIG_LEN].reshape(n_ops, self.SIG_LEN) if n_ops else sig
+        else:
+            sig, status = np.zeros((max(n_ops, 1), self.SIG_LEN), dtype=np.uint8), np.zeros(max(n_ops, 1), dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
+        _ph_lib.check(_ph_lib.load().mldsa_hash_sign_host(self._ph_host(staging_bytes), self.pset, code, vp(sk), n_keys, vp(kidx),
+                                                          vp(mflat), vp(moff), vp(cflat), vp(coff), vp(rn), vp(sig), vp(status), n_ops))
+        if n_ops and int(status[:n_ops].min()) < 0:
+            raise ValueError("HashML-DSA.Sign: ctx too long")
+        return sig[:n_ops]
+
+
+class _PhHost:
+    """One mldsa_ph_host (staging chunks, streams, per-batch buffers) on a HotPath's context.  It keeps the HotPath alive;
+    destroying it does not need the context, so it may follow HotPath.close()."""
+
+    def __init__(self, hp, staging_bytes):
+        self.hp = hp
+        out = C.c_void_p(0)
+        _ph_lib.check(_ph_lib.load().mldsa_ph_host_create(hp._h, int(staging_bytes), C.byref(out)))
+        self.handle = out
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _ph_lib.load().mldsa_ph_host_destroy(self.handle)
+            self.handle = None
+        except Exception:
+            pass
+
+
+class PrehashStream:
+    """Hash states of n_ops messages in device memory (mldsa_ph_init / _update / _final).  Every call is asynchronous on the
+    current stream; the states are used in stream order."""
+
+    def __init__(self, m, n_ops, ph):
+        self.m, self.n_ops = m, int(n_ops)
+        self.lib, self.code = _ph_lib.load(), m._ph_arg(ph)
+        self.row_len = self.lib.mldsa_ph_row_len(self.code)
+        if self.row_len < 0:
+            raise ValueError(f"unknown ph {ph!r}")
+        self.state_bytes = self.lib.mldsa_ph_state_bytes(self.code, self.n_ops)
+        self.state = torch.empty(max(self.state_bytes, 8), dtype=torch.uint8, device=m.device)
+        _ph_lib.check(self.lib.mldsa_ph_init(m.hp._h, self.code, _ptr(self.state), self.state_bytes, self.n_ops, _stream(m.device)))
+
+    def update(self, piece_buf, piece_off):
+        """op i absorbs piece_buf[piece_off[i] : piece_off[i + 1]] (device tensors; piece_off: n_ops + 1 uint64 offsets)"""
+        _ph_lib.check(self.lib.mldsa_ph_update(self.m.hp._h, self.code, _ptr(self.state), self.state_bytes,
+                                               _ptr(piece_buf) if piece_buf is not None else C.c_void_p(0), _ptr(piece_off),
+                                               self.n_ops, _stream(self.m.device)))
+        return self
+
+    def final(self):
+        """(rows [n_ops, row_len] = OID || PH(M_i), bad [n_ops]): the shapes of prehash_device"""
+        rows = torch.empty((max(self.n_ops, 1), self.row_len), dtype=torch.uint8, device=self.m.device)
+        bad = torch.empty(max(self.n_ops, 1), dtype=torch.uint8, device=self.m.device)
+        _ph_lib.check(self.lib.mldsa_ph_final(self.m.hp._h, self.code, _ptr(self.state), self.state_bytes, _ptr(rows), C.c_void_p(0),
+                                              _ptr(bad), self.n_ops, _stream(self.m.device)))
+        return rows[:self.n_ops], bad[:self.n_ops]
+
+
 class MlDsaGroup(MlDsa):
     """The host-memory entry points over SEVERAL GPUs of one node: mldsa_group_create(device_ids) + mldsa_*_host_group
     (include/mldsa_hip.h "several GPUs of one node").  verify_host / sign_host / keygen_host take exactly the arguments of

@@ -15,6 +15,7 @@
 
 #include "../../include/mldsa_ph.h"
 #include "../csrc/keccak.h"
+#include "ph_internal.h"
 #include "sha2_dev.h"
 
 namespace {
@@ -24,14 +25,13 @@ using mldsa::load_le32;
 using mldsa_ph::bswap32;
 using mldsa_ph::static_for;
 
-constexpr int OID_LEN = 11;
-constexpr uint8_t OID_PREFIX[10] = {0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x02};
-
-template <int PH> struct PhTraits;
-template <> struct PhTraits<MLDSA_PH_SHA256> { static constexpr int BLOCK = 64, TAIL = 9, DIGEST = 32; static constexpr uint8_t OID_LAST = 0x01; };
-template <> struct PhTraits<MLDSA_PH_SHA512> { static constexpr int BLOCK = 128, TAIL = 17, DIGEST = 64; static constexpr uint8_t OID_LAST = 0x03; };
-// SHAKE128: rate 168; the pad (0x1F ... 0x80) always fits in the block that holds the message's end
-template <> struct PhTraits<MLDSA_PH_SHAKE128> { static constexpr int BLOCK = 168, TAIL = 1, DIGEST = 32; static constexpr uint8_t OID_LAST = 0x0b; };
+using mldsa_ph::core_failed;
+using mldsa_ph::DeviceScope;
+using mldsa_ph::fail;
+using mldsa_ph::OID_LEN;
+using mldsa_ph::OID_PREFIX;
+using mldsa_ph::PhTraits;
+using mldsa_ph::row_len_of;
 
 // little-endian dword at byte `pos` of the padded message: message bytes, then PADB, then zeros
 template <uint8_t PADB>
@@ -220,20 +220,6 @@ __global__ __launch_bounds__(64) void k_ph_refuse(const uint8_t* __restrict__ ba
 // ------------------------------------------------------------------------------------------------------------ host side
 thread_local std::string g_err;
 
-int fail(int rc, const std::string& msg) {
-    g_err = msg;
-    return rc;
-}
-
-int row_len_of(int ph) {
-    switch (ph) {
-        case MLDSA_PH_SHA256: return OID_LEN + 32;
-        case MLDSA_PH_SHA512: return OID_LEN + 64;
-        case MLDSA_PH_SHAKE128: return OID_LEN + 32;
-        default: return -1;
-    }
-}
-
 // scratch = [offset table: 8 (n + 1)] [rows: n row_len] [bad: n]; 0 when it does not fit a size_t
 size_t scratch_of(int ph, size_t n) {
     const int rl = row_len_of(ph);
@@ -242,19 +228,6 @@ size_t scratch_of(int ph, size_t n) {
     if (n >= lim) return 0;
     return 8 * (n + 1) + n * (size_t)rl + n;
 }
-
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 int launch_prehash(int ph, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off, uint8_t* out,
                    uint64_t* out_off, uint8_t* bad, size_t n_ops, hipStream_t s) {
@@ -282,11 +255,6 @@ int launch_refuse(const uint8_t* bad, uint8_t* ok, uint8_t* sigs, size_t sig_len
     return MLDSA_OK;
 }
 
-int core_failed(const char* fn, int rc) {
-    const char* m = mldsa_last_error();
-    return fail(rc, std::string(fn) + ": " + (m ? m : "(no message)"));
-}
-
 // the checks shared by the op-level calls, all before anything is launched
 struct Scratch {
     uint64_t* off;
@@ -312,6 +280,29 @@ int check_call(const char* fn, mldsa_ctx* ctx, int set, int ph, size_t n_keys, c
 }
 
 }  // namespace
+
+namespace mldsa_ph {
+
+int fail(int rc, const std::string& msg) {
+    g_err = msg;
+    return rc;
+}
+
+int core_failed(const char* fn, int rc) {
+    const char* m = mldsa_last_error();
+    return fail(rc, std::string(fn) + ": " + (m ? m : "(no message)"));
+}
+
+int row_len_of(int ph) {
+    switch (ph) {
+        case MLDSA_PH_SHA256: return OID_LEN + 32;
+        case MLDSA_PH_SHA512: return OID_LEN + 64;
+        case MLDSA_PH_SHAKE128: return OID_LEN + 32;
+        default: return -1;
+    }
+}
+
+}  // namespace mldsa_ph
 
 extern "C" {
 

@@ -23,6 +23,10 @@
  *   mldsa_prehash and the verify calls are asynchronous on `stream` and never synchronise the host;
  *   mldsa_hash_sign is synchronous like mldsa_sign: signatures and statuses are final when it returns.
  *   Scratch is used in stream order on `stream`: it may be reused by the next call on the same stream.
+ *
+ * Messages that arrive in pieces, or that are too large to hold on the device at once, go through the incremental
+ *   pre-hash (mldsa_ph_init / _update / _final below); messages, keys and signatures that lie in HOST memory go through
+ *   mldsa_hash_verify_host / mldsa_hash_sign_host, which stream the message bytes through a bounded staging buffer.
  */
 #ifndef MLDSA_PH_H
 #define MLDSA_PH_H
@@ -70,6 +74,64 @@ int mldsa_hash_sign(mldsa_ctx *ctx, int set, int ph, const uint8_t *rho, const u
                     const uint32_t *key_idx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *ctxs,
                     const uint64_t *ctx_off, const uint8_t *rnd, uint8_t *sigs, int32_t *status, size_t n_ops,
                     void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- incremental pre-hash: init / update / final ------------------------------------------------------------
+ * PH(M) of n_ops messages that arrive in pieces, one operation per lane.  The hash states of the operations live in
+ * caller-owned device memory between the calls: `state`, at least mldsa_ph_state_bytes(ph, n_ops) bytes, 8-byte aligned,
+ * opaque (its layout depends on n_ops: a state belongs to the (ph, n_ops) it was initialised with, and every call on it
+ * passes the same two values).  The length of a message is a 64-bit byte count.
+ *   mldsa_ph_init    fresh states: the empty message, not bad.
+ *   mldsa_ph_update  op i absorbs the piece pieces[piece_off[i], piece_off[i + 1]); n_ops + 1 offsets on the device.  An
+ *                    empty piece is a no-op.  Pieces may be cut at any byte position and lie at any byte alignment.
+ *   mldsa_ph_final   pads and finishes: out[n_ops][row_len] = OID || PH(M_i), the row format of mldsa_prehash; bad[i]
+ *                    (bad may be NULL); and, when out_off != NULL, the n_ops + 1 offsets i row_len that the core's
+ *                    MLDSA_MODE_PREHASH call reads.  The states are not changed: init starts the next messages.
+ * For every way of cutting the messages into pieces the rows are those of mldsa_prehash on the whole messages.
+ * Offsets are untrusted, with the rule of mldsa_prehash: a piece pair that is not in order inside
+ *   [piece_off[0], piece_off[n_ops]], or that names bytes of a NULL `pieces`, reads nothing and marks its op bad.  Bad is
+ *   sticky across later updates (no further byte of that op is read); final gives such an op an all-zero row and
+ *   bad[i] = 1.  Other ops are unaffected.  Nothing outside [piece_off[0], piece_off[n_ops]) is read and nothing outside
+ *   the first mldsa_ph_state_bytes(ph, n_ops) bytes of `state` is touched.
+ * Argument errors: unknown ph, NULL ctx, a NULL or misaligned `state`, state_bytes < mldsa_ph_state_bytes(ph, n_ops), a
+ *   NULL piece_off / out return MLDSA_ERR_PARAM before anything is launched; n_ops = 0 returns MLDSA_OK.
+ * All three calls are asynchronous on `stream`, never synchronise the host, launch on mldsa_ctx_device(ctx) and restore
+ *   the caller's current device.  The state is used in stream order. */
+/* bytes of device memory for the states of n_ops operations; 0 for an unknown ph or a size that does not fit */
+size_t mldsa_ph_state_bytes(int ph, size_t n_ops);
+int mldsa_ph_init(mldsa_ctx *ctx, int ph, void *state, size_t state_bytes, size_t n_ops, void *stream);
+int mldsa_ph_update(mldsa_ctx *ctx, int ph, void *state, size_t state_bytes, const uint8_t *pieces, const uint64_t *piece_off,
+                    size_t n_ops, void *stream);
+int mldsa_ph_final(mldsa_ctx *ctx, int ph, void *state, size_t state_bytes, uint8_t *out, uint64_t *out_off, uint8_t *bad,
+                   size_t n_ops, void *stream);
+
+/* ---- HashML-DSA from host memory ----------------------------------------------------------------------------
+ * Raw messages, wire-format keys, signatures and results in HOST memory: arguments and results are those of
+ * mldsa_verify_host / mldsa_sign_host with `ph` in place of `mode`.  A mldsa_ph_host owns what the calls need besides the
+ * context: two staging chunks of `staging_bytes` each on the device, two page-locked ones on the host, a copy and a
+ * compute stream, and the per-batch buffers (offsets, hash states, rows), which grow with the largest n_ops seen.
+ *   The message bytes [msg_off[0], msg_off[n_ops]) are cut into chunks of at most staging_bytes at arbitrary byte
+ *   positions -- a message may span any number of chunks, a chunk may hold thousands of messages -- and chunk i + 1 is
+ *   uploaded while mldsa_ph_update runs on chunk i, for the ops that have bytes in it.  The device memory of a call is
+ *   2 staging_bytes + states + rows + one offset table, whatever the size of the messages.  After mldsa_ph_final the rows
+ *   (43 / 75 bytes per op) are brought to the host and mldsa_verify_host / mldsa_sign_host run in MLDSA_MODE_PREHASH:
+ *   verdicts, signatures, statuses and per-op refusals are the core's.
+ * Refusal rules are those of the core's *_host calls: both offset tables are checked first (mldsa_check_offsets) and a
+ *   malformed table, or a msg_off that names bytes of a NULL msgs, fails the whole call with MLDSA_ERR_PARAM before a
+ *   message byte is read; an op whose ctx is longer than 255 bytes gets ok = 0 / MLDSA_ERR_CTX_LEN from the core.
+ * Page-locked caller memory (mldsa_host_alloc) is copied by DMA where it lies, pageable memory goes through the
+ *   page-locked chunks.  A call returns when the results are in the caller's buffers.  One call at a time per
+ *   mldsa_ph_host (the calls take its mutex); objects on different contexts are independent.  No call may be made on
+ *   an object whose context has been destroyed; mldsa_ph_host_destroy itself does not need the context. */
+typedef struct mldsa_ph_host mldsa_ph_host;
+/* staging_bytes: size of ONE message staging chunk (two are kept, device + page-locked); 0 = the library's default */
+int mldsa_ph_host_create(mldsa_ctx *ctx, size_t staging_bytes, mldsa_ph_host **out);
+void mldsa_ph_host_destroy(mldsa_ph_host *h); /* NULL: no-op */
+int mldsa_hash_verify_host(mldsa_ph_host *h, int set, int ph, const uint8_t *pk, size_t n_keys, const uint32_t *key_idx,
+                           const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *ctxs, const uint64_t *ctx_off,
+                           const uint8_t *sigs, uint8_t *ok, size_t n_ops);
+int mldsa_hash_sign_host(mldsa_ph_host *h, int set, int ph, const uint8_t *sk, size_t n_keys, const uint32_t *key_idx,
+                         const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *ctxs, const uint64_t *ctx_off,
+                         const uint8_t *rnd, uint8_t *sigs, int32_t *status, size_t n_ops);
 
 #ifdef __cplusplus
 }

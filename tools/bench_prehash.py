@@ -13,6 +13,15 @@ fips204_amd/ph/prehash.hip); the issue costs are the column cyc/instr@clk of too
 Ceiling GB/s = SIMDs x clock x 64 lanes x block bytes / cycles per block, for one message per lane and full issue.
 
     python tools/bench_prehash.py --ubench profiles/prehash_ubench_valu.txt > profiles/prehash_bench.jsonl
+
+--stream runs the legs of the incremental pre-hash and of the host-memory calls instead, one JSON line each:
+  prehash_stream   mldsa_ph_init + updates + final (1 piece, 4 equal pieces; hipEvent time) against mldsa_prehash of the same run
+  hash_host        mldsa_hash_verify_host / _sign_host on page-locked buffers (wall clock) against (i) the hashlib loop +
+                   verify_host / sign_host in MLDSA_MODE_PREHASH and (ii) those calls on precomputed rows + message bytes / the
+                   measured page-locked H2D rate
+  staging_sweep    mldsa_hash_verify_host at --sweep-len bytes per message for staging chunks of --sweep-mib MiB
+
+    python tools/bench_prehash.py --stream >> profiles/prehash_stream_bench.jsonl
 """
 import argparse
 import json
@@ -60,6 +69,152 @@ def ceiling(ph, costs):
                  "formula": "simds * clock_GHz * 64 lanes * block_bytes / cycles_per_block"}
 
 
+def stream_legs(args):
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from benchlib.hostfed import measure_h2d_GBs
+    from fips204_amd import _ph_lib
+    from fips204_amd.ml_dsa import MODE_PREHASH, MlDsa, hash_message
+
+    m = MlDsa(65)
+    lib = _ph_lib.load()
+    n, nk = args.n, 64
+    phs = args.phs.split(",")
+    legs = args.legs.split(",")
+    xi = np.frombuffer(b"".join(bytes([i]) * 32 for i in range(nk)), dtype=np.uint8)
+    pk, sk = m.keygen_host(xi)
+    kidx = (np.arange(n) % nk).astype(np.uint32)
+
+    def timed(fn, steps, warmup):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / steps  # ms
+
+    def wall(fn, steps):
+        fn()
+        best = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            fn()
+            best.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(best))
+
+    def pinned(nbytes):
+        p = C.c_void_p()
+        assert m.lib.mldsa_host_alloc(C.byref(p), max(nbytes, 1)) == 0
+        return p, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(nbytes, 1),))[:nbytes]
+
+    if "prehash_stream" in legs:
+        for L in [int(x) for x in args.lens.split(",")]:
+            g = torch.Generator(device="cuda").manual_seed(L)
+            buf = torch.randint(0, 256, (n * L + 16,), dtype=torch.uint8, device="cuda", generator=g)
+            off = torch.arange(n + 1, dtype=torch.int64, device="cuda") * L
+            q = L // 4
+            # 4 equal pieces: piece u of every op packed back to back, as a caller who receives the batch in four parts holds it
+            view = buf[:n * L].view(n, L)
+            parts = [view[:, u * q:(u + 1) * q].contiguous().view(-1) for u in range(4)]
+            parts = [torch.cat([x, torch.zeros(16, dtype=torch.uint8, device="cuda")]) for x in parts]
+            off4 = torch.arange(n + 1, dtype=torch.int64, device="cuda") * q
+            for ph in phs:
+                one_ms = timed(lambda: m.prehash_device(buf, off, n, ph), args.steps, args.warmup)
+
+                def run(pieces):
+                    st = m.prehash_stream(n, ph)
+                    for b_, o_ in pieces:
+                        st.update(b_, o_)
+                    return st.final()
+                s1_ms = timed(lambda: run([(buf, off)]), args.steps, args.warmup)
+                s4_ms = timed(lambda: run([(x, off4) for x in parts]), args.steps, args.warmup)
+                assert torch.equal(run([(buf, off)])[0], m.prehash_device(buf, off, n, ph)[0])
+                assert torch.equal(run([(x, off4) for x in parts])[0], m.prehash_device(buf, off, n, ph)[0])
+                sb = lib.mldsa_ph_state_bytes(m._ph_arg(ph), n)
+                print(json.dumps({"workload": "prehash_stream", "ph": ph, "n_ops": n, "msg_len": L, "state_bytes": sb,
+                                  "one_shot_us": round(one_ms * 1e3, 1), "stream_1_piece_us": round(s1_ms * 1e3, 1),
+                                  "stream_4_pieces_us": round(s4_ms * 1e3, 1), "ratio_1_piece": round(s1_ms / one_ms, 3),
+                                  "ratio_4_pieces": round(s4_ms / one_ms, 3),
+                                  "extra_1_piece_us": round((s1_ms - one_ms) * 1e3, 1)}), flush=True)
+            del buf, parts, view
+            torch.cuda.empty_cache()
+
+    def host_batch(L):
+        """n messages of L bytes in page-locked memory (handle to free, bytes) and their offsets"""
+        hm, msgs = pinned(n * L)
+        msgs[:] = np.random.default_rng(L).integers(0, 256, n * L, dtype=np.uint8)
+        moff = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+        return hm, msgs, moff
+
+    if "hash_host" in legs:
+        L = 1024
+        hm, msgs, moff = host_batch(L)
+        hs, sig_buf = pinned(n * m.SIG_LEN)
+        ho, ok_buf = pinned(n)
+        hst, st_raw = pinned(4 * n)
+        st_buf = st_raw.view(np.int32)
+        sig2d = sig_buf.reshape(n, m.SIG_LEN)
+        rnd = np.zeros(n * 32, dtype=np.uint8)
+        h2d = measure_h2d_GBs()
+        raw = msgs.tobytes()
+        mlist = [raw[i * L:(i + 1) * L] for i in range(n)]
+        for ph in phs:
+            sign_ms = wall(lambda: m.hash_sign_host(sk, (msgs, moff), rnd, ph=ph, key_idx=kidx, out=(sig2d, st_buf)), 3)
+            ver_ms = wall(lambda: m.hash_verify_host(pk, (msgs, moff), sig2d, ph=ph, key_idx=kidx, out=ok_buf), 5)
+            assert ok_buf.all()
+            t0 = time.perf_counter()
+            rows = [hash_message(x, ph) for x in mlist]
+            loop_ms = (time.perf_counter() - t0) * 1e3
+            rl = len(rows[0])
+            hr, rflat = pinned(n * rl)
+            rflat[:] = np.frombuffer(b"".join(rows), dtype=np.uint8)
+            roff = np.arange(n + 1, dtype=np.uint64) * np.uint64(rl)
+            vfloor_ms = wall(lambda: m.verify_host(pk, (rflat, roff), sig2d, key_idx=kidx, mode=MODE_PREHASH, out=ok_buf), 5)
+            assert ok_buf.all()
+            sfloor_ms = wall(lambda: m.sign_host(sk, (rflat, roff), rnd, key_idx=kidx, mode=MODE_PREHASH, out=(sig2d, st_buf)), 3)
+            m.lib.mldsa_host_free(hr)
+            up_ms = n * L / (h2d * 1e9) * 1e3
+            print(json.dumps({"workload": "hash_host", "set": 65, "ph": ph, "n_ops": n, "msg_len": L, "memory": "page-locked",
+                              "hash_verify_host_ms": round(ver_ms, 3), "hash_sign_host_ms": round(sign_ms, 3),
+                              "host_prehash_loop_ms": round(loop_ms, 1),
+                              "parent_route_verify_ms": round(loop_ms + vfloor_ms, 1), "parent_route_sign_ms": round(loop_ms + sfloor_ms, 1),
+                              "verify_host_on_rows_ms": round(vfloor_ms, 3), "sign_host_on_rows_ms": round(sfloor_ms, 3),
+                              "h2d_GBs_measured": round(h2d, 2), "message_upload_ms": round(up_ms, 3),
+                              "verify_over_floor": round(ver_ms / (vfloor_ms + up_ms), 3),
+                              "sign_over_floor": round(sign_ms / (sfloor_ms + up_ms), 3),
+                              "verify_speedup_vs_parent_route": round((loop_ms + vfloor_ms) / ver_ms, 1),
+                              "sign_speedup_vs_parent_route": round((loop_ms + sfloor_ms) / sign_ms, 1)}), flush=True)
+        for h_ in (hm, hs, ho, hst):
+            m.lib.mldsa_host_free(h_)
+
+    if "staging_sweep" in legs:
+        L = args.sweep_len
+        hm, msgs, moff = host_batch(L)
+        hs, sig_buf = pinned(n * m.SIG_LEN)
+        sig2d = sig_buf.reshape(n, m.SIG_LEN)
+        st_buf = np.zeros(n, dtype=np.int32)
+        rnd = np.zeros(n * 32, dtype=np.uint8)
+        h2d = measure_h2d_GBs()
+        for ph in phs:
+            m.hash_sign_host(sk, (msgs, moff), rnd, ph=ph, key_idx=kidx, out=(sig2d, st_buf))
+            for mib in [int(x) for x in args.sweep_mib.split(",")]:
+                ok = np.zeros(n, dtype=np.uint8)
+                ms = wall(lambda: m.hash_verify_host(pk, (msgs, moff), sig2d, ph=ph, key_idx=kidx, out=ok, staging_bytes=mib << 20), 3)
+                assert ok.all()
+                print(json.dumps({"workload": "staging_sweep", "set": 65, "ph": ph, "n_ops": n, "msg_len": L, "memory": "page-locked",
+                                  "staging_MiB": mib, "hash_verify_host_ms": round(ms, 2), "message_GBs": round(n * L / ms / 1e6, 2),
+                                  "h2d_GBs_measured": round(h2d, 2)}), flush=True)
+        m.lib.mldsa_host_free(hm)
+        m.lib.mldsa_host_free(hs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=65536)
@@ -70,7 +225,13 @@ def main():
     ap.add_argument("--big", type=int, default=262144, help="also the 1 KiB point at this many ops (0: skip)")
     ap.add_argument("--ubench", default=os.path.join(ROOT, "profiles", "prehash_ubench_valu.txt"))
     ap.add_argument("--no-host", action="store_true", help="skip the host pre-hash calls")
+    ap.add_argument("--stream", action="store_true", help="the legs of the incremental pre-hash and the host-memory calls instead")
+    ap.add_argument("--legs", default="prehash_stream,hash_host,staging_sweep")
+    ap.add_argument("--sweep-len", type=int, default=16384)
+    ap.add_argument("--sweep-mib", default="1,4,16,64")
     args = ap.parse_args()
+    if args.stream:
+        return stream_legs(args)
 
     import numpy as np
     import torch
