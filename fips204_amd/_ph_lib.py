@@ -15,6 +15,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mldsa_ph.h")
 
 ABI_VERSION = 1
 PH_SHA256, PH_SHA512, PH_SHAKE128 = 0, 1, 2
+# the other functions of the NIST hash OID arc: 16 + the last OID arc (include/mldsa_ph.h)
+PH_SHA384, PH_SHA224, PH_SHA512_224, PH_SHA512_256 = 18, 20, 21, 22
+PH_SHA3_224, PH_SHA3_256, PH_SHA3_384, PH_SHA3_512, PH_SHAKE256 = 23, 24, 25, 26, 28
 
 _P, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
 

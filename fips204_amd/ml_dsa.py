@@ -19,14 +19,33 @@ MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
 # Ph (src/types.rs:5-12) and hash_message (src/hashing.rs:316-354): the pre-hash of HashML-DSA is message-length-bound
 # host work; the device sees OID || PH(M) as the message of a MODE_PREHASH call.
 PH_SHA256, PH_SHA512, PH_SHAKE128 = "SHA256", "SHA512", "SHAKE128"
+# FIPS 204 §5.4 allows any approved hash or XOF: the nine other functions of the NIST arc 2.16.840.1.101.3.4.2.*
+PH_SHA384, PH_SHA224, PH_SHA512_224, PH_SHA512_256 = "SHA384", "SHA224", "SHA512_224", "SHA512_256"
+PH_SHA3_224, PH_SHA3_256, PH_SHA3_384, PH_SHA3_512, PH_SHAKE256 = "SHA3_224", "SHA3_256", "SHA3_384", "SHA3_512", "SHAKE256"
 _PH_OID = bytes([0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x02])
-# the same pre-hash on the device (include/mldsa_ph.h): Ph -> MLDSA_PH_*; list-level calls choose with prehash="host" | "device"
-_PH_ABI = {PH_SHA256: _ph_lib.PH_SHA256, PH_SHA512: _ph_lib.PH_SHA512, PH_SHAKE128: _ph_lib.PH_SHAKE128}
+# Ph -> (last OID byte, hashlib name, bytes of output asked of an XOF or None, MLDSA_PH_* of include/mldsa_ph.h); list-level
+# calls choose between the hashlib loop and the same pre-hash on the device with prehash="host" | "device"
+_PH_TABLE = {
+    PH_SHA256: (0x01, "sha256", None, _ph_lib.PH_SHA256),
+    PH_SHA384: (0x02, "sha384", None, _ph_lib.PH_SHA384),
+    PH_SHA512: (0x03, "sha512", None, _ph_lib.PH_SHA512),
+    PH_SHA224: (0x04, "sha224", None, _ph_lib.PH_SHA224),
+    PH_SHA512_224: (0x05, "sha512_224", None, _ph_lib.PH_SHA512_224),
+    PH_SHA512_256: (0x06, "sha512_256", None, _ph_lib.PH_SHA512_256),
+    PH_SHA3_224: (0x07, "sha3_224", None, _ph_lib.PH_SHA3_224),
+    PH_SHA3_256: (0x08, "sha3_256", None, _ph_lib.PH_SHA3_256),
+    PH_SHA3_384: (0x09, "sha3_384", None, _ph_lib.PH_SHA3_384),
+    PH_SHA3_512: (0x0A, "sha3_512", None, _ph_lib.PH_SHA3_512),
+    PH_SHAKE128: (0x0B, "shake_128", 32, _ph_lib.PH_SHAKE128),
+    PH_SHAKE256: (0x0C, "shake_256", 64, _ph_lib.PH_SHAKE256),
+}
+_PH_ABI = {name: row[3] for name, row in _PH_TABLE.items()}
+_PH_NAMES = "Ph: " + ", ".join(_PH_TABLE)
 
 
 def _ph_code(ph):
     if ph not in _PH_ABI:
-        raise ValueError("Ph: SHA256, SHA512 or SHAKE128")
+        raise ValueError(_PH_NAMES)
     return _PH_ABI[ph]
 
 
@@ -45,16 +64,14 @@ class OsRng:
 
 
 def hash_message(message, ph):
-    """OID || PH(M): DER object identifier of the hash (11 bytes) followed by its digest (32 / 64 / 32 bytes)."""
+    """OID || PH(M): DER object identifier of the hash (11 bytes) followed by its digest (28 ... 64 bytes; 32 of SHAKE128, 64 of SHAKE256)."""
     import hashlib
     message = bytes(message)
-    if ph == PH_SHA256:
-        return _PH_OID + b"\x01" + hashlib.sha256(message).digest()
-    if ph == PH_SHA512:
-        return _PH_OID + b"\x03" + hashlib.sha512(message).digest()
-    if ph == PH_SHAKE128:
-        return _PH_OID + b"\x0b" + hashlib.shake_128(message).digest(32)
-    raise ValueError("Ph: SHA256, SHA512 or SHAKE128")
+    if not isinstance(ph, str) or ph not in _PH_TABLE:
+        raise ValueError(_PH_NAMES)
+    oid_last, name, xof_len, _ = _PH_TABLE[ph]
+    h = hashlib.new(name, message)
+    return _PH_OID + bytes([oid_last]) + (h.digest(xof_len) if xof_len else h.digest())
 
 
 def _cat_with_offsets(items, device):

@@ -68,7 +68,7 @@ void release(mldsa_ph_host* h) {
 // buffers for n_ops operations of any PH (rows are sized for the longest row)
 int reserve(mldsa_ph_host* h, size_t n_ops) {
     size_t need_state = 0;
-    for (int ph = 0; ph < 3; ph++) need_state = std::max(need_state, mldsa_ph::state_bytes_of(ph, n_ops));
+    for (int ph : mldsa_ph::ALL_PH) need_state = std::max(need_state, mldsa_ph::state_bytes_of(ph, n_ops));
     if (need_state == 0) return fail(MLDSA_ERR_PARAM, "mldsa_hash_*_host: n_ops too large");
     if (n_ops <= h->cap_ops) return MLDSA_OK;
     if (h->d_off) (void)hipFree(h->d_off);

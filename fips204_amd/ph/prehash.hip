@@ -1,10 +1,16 @@
-// HashML-DSA pre-hash on the GPU (include/mldsa_ph.h): PH(M) = SHA-256 / SHA-512 / SHAKE128 of each raw message
-// (reference src/hashing.rs:316-354), then the core's MLDSA_MODE_PREHASH call on the rows OID || PH(M).
+// HashML-DSA pre-hash on the GPU (include/mldsa_ph.h): PH(M) of each raw message for the twelve functions of the NIST hash
+// OID arc (the reference's three, src/hashing.rs:316-354, and the nine others FIPS 204 §5.4 allows), then the core's
+// MLDSA_MODE_PREHASH call on the rows OID || PH(M).
 //
-// k_prehash<PH>: one message per lane, 64 per wave (the layout of the core's k_mu).  Each lane absorbs its own blocks
+// k_prehash<FAM, BLOCK, PH>: one message per lane, 64 per wave (the layout of the core's k_mu).  Each lane absorbs its own blocks
 // and pads its own message; the wave loops to its longest message.  Whole dwords of the message come from one
 // byte-granular dword load each; only the dwords around the message's end are assembled from bytes.  The same launch
-// writes each op's row and the offset table the core call reads (off[i] = i row_len).
+// writes each op's row and the offset table the core call reads (off[i] = i row_len).  One instance per compression function
+// and block size (ph_internal.h); initial value, pad byte, digest length and OID byte are arguments (PhVar), except in the
+// instances of the reference's three functions, which keep them as constants.
+// k_prehash_wave<RATE>: the small-call form of the Keccak family, one message per WAVE on the bit-interleaved cooperative
+// sponge of csrc/keccak_coop2.h, the way mu_coop2 (csrc/verify_dev.h) computes mu for small calls.  Calls of at most
+// MLDSA_PH_COOP_MAX_OPS operations take it; checks, refusals, rows and offset table are k_prehash's, byte for byte.
 // k_ph_refuse: after the core call, the per-op refusal of ops whose message pair was malformed (the core saw a
 // well-formed table of rows, so it cannot know).
 #include <hip/hip_runtime.h>
@@ -15,11 +21,13 @@
 
 #include "../../include/mldsa_ph.h"
 #include "../csrc/keccak.h"
+#include "../csrc/keccak_coop2.h"
 #include "ph_internal.h"
 #include "sha2_dev.h"
 
 namespace {
 
+using mldsa::Coop2Lane;
 using mldsa::KeccakState;
 using mldsa::load_le32;
 using mldsa_ph::bswap32;
@@ -28,70 +36,100 @@ using mldsa_ph::static_for;
 using mldsa_ph::core_failed;
 using mldsa_ph::DeviceScope;
 using mldsa_ph::fail;
+using mldsa_ph::FAM_KECCAK;
+using mldsa_ph::FAM_SHA2_32;
+using mldsa_ph::FAM_SHA2_64;
+using mldsa_ph::FamTraits;
 using mldsa_ph::OID_LEN;
 using mldsa_ph::OID_PREFIX;
-using mldsa_ph::PhTraits;
+using mldsa_ph::PhInfo;
+using mldsa_ph::PhVar;
 using mldsa_ph::row_len_of;
 
-// little-endian dword at byte `pos` of the padded message: message bytes, then PADB, then zeros
-template <uint8_t PADB>
-__device__ __forceinline__ uint32_t padded_le32(const uint8_t* mp, size_t mlen, size_t pos) {
+// little-endian dword at byte `pos` of the padded message: message bytes, then padb, then zeros
+__device__ __forceinline__ uint32_t padded_le32(const uint8_t* mp, size_t mlen, size_t pos, uint32_t padb) {
     if (pos + 4 <= mlen) return load_le32(mp + pos);
     if (pos > mlen) return 0;
     uint32_t v = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const size_t p = pos + k;
-        const uint32_t byte = p < mlen ? mp[p] : p == mlen ? PADB : 0u;
+        const uint32_t byte = p < mlen ? mp[p] : p == mlen ? padb : 0u;
         v |= byte << (8 * k);
     }
     return v;
 }
 
-template <int PH>
+// The checks of k_mu for op `op` of a call of n_ops: the call vouches for [off[0], off[n_ops]); a pair outside it in order is
+// refused unread.  live: the op is hashed (mp, mlen valid); msg_bad: its message pair was malformed.
+struct OpMsg {
+    const uint8_t* mp;
+    size_t mlen;
+    bool msg_bad, live;
+};
+
+__device__ __forceinline__ OpMsg check_op(const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off,
+                                          size_t op, size_t n_ops) {
+    OpMsg o = {nullptr, 0, false, false};
+    const uint64_t m0 = msg_off[op], m1 = msg_off[op + 1];
+    o.msg_bad = !(msg_off[0] <= m0 && m0 <= m1 && m1 <= msg_off[n_ops]);
+    o.msg_bad |= m1 != m0 && msgs == nullptr;
+    bool ctx_bad = false;
+    if (ctx_off) {
+        const uint64_t c0 = ctx_off[op], c1 = ctx_off[op + 1];
+        ctx_bad = !(ctx_off[0] <= c0 && c0 <= c1 && c1 <= ctx_off[n_ops]);
+        ctx_bad |= c1 != c0 && ctxs == nullptr;
+        ctx_bad |= !ctx_bad && c1 - c0 > 255;
+    }
+    o.live = !o.msg_bad && !ctx_bad;
+    if (o.live) {
+        o.mp = msgs + m0;
+        o.mlen = (size_t)(m1 - m0);
+    }
+    return o;
+}
+
+// What PhVar holds for the reference's three functions, as constants: their instances (PH >= 0) are compiled with them, so that
+// their code is what it was before the other nine came (with the four values as data the three measured 6-19 % slower at
+// 65 536 x 1 KiB, profiles/prehash_fips_list_bench.jsonl).  PH = -1: the values are the kernel argument.
+template <int PH> struct FixedVar { static constexpr int DIGEST = 0, IV = 0; static constexpr uint32_t OID_LAST = 0; };
+template <> struct FixedVar<MLDSA_PH_SHA256> { static constexpr int DIGEST = 32, IV = 0; static constexpr uint32_t OID_LAST = 0x01; };
+template <> struct FixedVar<MLDSA_PH_SHA512> { static constexpr int DIGEST = 64, IV = 0; static constexpr uint32_t OID_LAST = 0x03; };
+template <> struct FixedVar<MLDSA_PH_SHAKE128> { static constexpr int DIGEST = 32, IV = 0; static constexpr uint32_t OID_LAST = 0x0b; };
+
+template <int FAM, int BLOCK, int PH>
 __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off,
                                                 const uint8_t* __restrict__ ctxs, const uint64_t* __restrict__ ctx_off,
                                                 uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
-                                                uint8_t* __restrict__ bad, size_t n_ops) {
-    using T = PhTraits<PH>;
-    constexpr int ROW = OID_LEN + T::DIGEST;
+                                                uint8_t* __restrict__ bad, size_t n_ops, PhVar var) {
+    using T = FamTraits<FAM, BLOCK>;
+    using FV = FixedVar<PH>;
+    constexpr int MAX_DIGEST = PH >= 0 ? FV::DIGEST : T::MAX_DIGEST;
+    const int digest = PH >= 0 ? FV::DIGEST : (int)var.digest;
+    const int iv = PH >= 0 ? FV::IV : (int)var.iv;
+    const uint32_t oid_last = PH >= 0 ? FV::OID_LAST : (uint32_t)var.oid_last;
+    const size_t row_len = (size_t)OID_LEN + digest;
     const int lane = threadIdx.x;
     const size_t op = (size_t)blockIdx.x * 64 + lane;
     const bool valid = op < n_ops;
 
-    // the checks of k_mu: the call vouches for [off[0], off[n_ops]); a pair outside it in order is refused unread
-    const uint8_t* mp = nullptr;
-    size_t mlen = 0;
-    bool msg_bad = false, live = false;
-    if (valid) {
-        const uint64_t m0 = msg_off[op], m1 = msg_off[op + 1];
-        msg_bad = !(msg_off[0] <= m0 && m0 <= m1 && m1 <= msg_off[n_ops]);
-        msg_bad |= m1 != m0 && msgs == nullptr;
-        bool ctx_bad = false;
-        if (ctx_off) {
-            const uint64_t c0 = ctx_off[op], c1 = ctx_off[op + 1];
-            ctx_bad = !(ctx_off[0] <= c0 && c0 <= c1 && c1 <= ctx_off[n_ops]);
-            ctx_bad |= c1 != c0 && ctxs == nullptr;
-            ctx_bad |= !ctx_bad && c1 - c0 > 255;
-        }
-        live = !msg_bad && !ctx_bad;
-        if (live) {
-            mp = msgs + m0;
-            mlen = (size_t)(m1 - m0);
-        }
-    }
+    OpMsg o = {nullptr, 0, false, false};
+    if (valid) o = check_op(msgs, msg_off, ctxs, ctx_off, op, n_ops);
+    const uint8_t* mp = o.mp;
+    const size_t mlen = o.mlen;
+    const bool msg_bad = o.msg_bad, live = o.live;
     const size_t my_blocks = live ? (mlen + T::TAIL + T::BLOCK - 1) / T::BLOCK : 0;
     size_t max_blocks = my_blocks;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
-        const size_t o = (size_t)__shfl_xor((unsigned long long)max_blocks, m);
-        max_blocks = o > max_blocks ? o : max_blocks;
+        const size_t o2 = (size_t)__shfl_xor((unsigned long long)max_blocks, m);
+        max_blocks = o2 > max_blocks ? o2 : max_blocks;
     }
 
-    uint8_t dig[T::DIGEST];
-    if constexpr (PH == MLDSA_PH_SHA256) {
+    uint8_t dig[MAX_DIGEST];
+    if constexpr (FAM == FAM_SHA2_32) {
         mldsa_ph::Sha256State st;
-        mldsa_ph::sha256_init(st);
+        mldsa_ph::sha256_init(st, iv);
         for (size_t b = 0; b < max_blocks; b++) {
             if (b < my_blocks) {
                 const size_t base = b * 64;
@@ -101,7 +139,7 @@ __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs
                     for (int i = 0; i < 16; i++) w[i] = bswap32(load_le32(mp + base + 4 * i));
                 } else {
 #pragma unroll
-                    for (int i = 0; i < 16; i++) w[i] = bswap32(padded_le32<0x80>(mp, mlen, base + 4 * i));
+                    for (int i = 0; i < 16; i++) w[i] = bswap32(padded_le32(mp, mlen, base + 4 * i, 0x80));
                     if (b == my_blocks - 1) {  // 64-bit big-endian bit length
                         w[14] = (uint32_t)(mlen >> 29);
                         w[15] = (uint32_t)(mlen << 3);
@@ -114,9 +152,9 @@ __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs
         for (int i = 0; i < 8; i++)
 #pragma unroll
             for (int k = 0; k < 4; k++) dig[4 * i + k] = (uint8_t)(st.h[i] >> (24 - 8 * k));
-    } else if constexpr (PH == MLDSA_PH_SHA512) {
+    } else if constexpr (FAM == FAM_SHA2_64) {
         mldsa_ph::Sha512State st;
-        mldsa_ph::sha512_init(st);
+        mldsa_ph::sha512_init(st, iv);
         for (size_t b = 0; b < max_blocks; b++) {
             if (b < my_blocks) {
                 const size_t base = b * 128;
@@ -130,8 +168,8 @@ __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs
                 } else {
 #pragma unroll
                     for (int i = 0; i < 16; i++) {
-                        w[i].hi = bswap32(padded_le32<0x80>(mp, mlen, base + 8 * i));
-                        w[i].lo = bswap32(padded_le32<0x80>(mp, mlen, base + 8 * i + 4));
+                        w[i].hi = bswap32(padded_le32(mp, mlen, base + 8 * i, 0x80));
+                        w[i].lo = bswap32(padded_le32(mp, mlen, base + 8 * i + 4, 0x80));
                     }
                     if (b == my_blocks - 1) {  // 128-bit big-endian bit length, high half 0
                         w[14] = {0u, 0u};
@@ -149,30 +187,32 @@ __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs
                 dig[8 * i + 4 + k] = (uint8_t)(st.h[i].lo >> (24 - 8 * k));
             }
     } else {
+        constexpr int RW = BLOCK / 8;  // 64-bit words of the rate
+        const uint32_t padb = PH == MLDSA_PH_SHAKE128 ? 0x1Fu : (uint32_t)var.padb;
         KeccakState st;
         mldsa::keccak_zero(st);
         for (size_t b = 0; b < max_blocks; b++) {
             if (b < my_blocks) {
-                const size_t base = b * 168;
-                if (base + 168 <= mlen) {
-                    static_for<0, 21>([&](auto wc) {
+                const size_t base = b * BLOCK;
+                if (base + BLOCK <= mlen) {
+                    static_for<0, RW>([&](auto wc) {
                         constexpr int W = decltype(wc)::value;
                         st.lo[W] ^= load_le32(mp + base + 8 * W);
                         st.hi[W] ^= load_le32(mp + base + 8 * W + 4);
                     });
                 } else {
-                    static_for<0, 21>([&](auto wc) {
+                    static_for<0, RW>([&](auto wc) {
                         constexpr int W = decltype(wc)::value;
-                        st.lo[W] ^= padded_le32<0x1F>(mp, mlen, base + 8 * W);
-                        st.hi[W] ^= padded_le32<0x1F>(mp, mlen, base + 8 * W + 4);
+                        st.lo[W] ^= padded_le32(mp, mlen, base + 8 * W, padb);
+                        st.hi[W] ^= padded_le32(mp, mlen, base + 8 * W + 4, padb);
                     });
                 }
-                if (b == my_blocks - 1) st.hi[20] ^= 0x80000000u;  // last byte of the rate block
+                if (b == my_blocks - 1) st.hi[RW - 1] ^= 0x80000000u;  // last byte of this rate's block
                 mldsa::keccak_f1600(st);
             }
         }
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < MAX_DIGEST / 8; i++)  // at most 64 bytes, inside the first block of every rate
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 dig[8 * i + k] = (uint8_t)(st.lo[i] >> (8 * k));
@@ -181,16 +221,74 @@ __global__ __launch_bounds__(64) void k_prehash(const uint8_t* __restrict__ msgs
     }
 
     if (valid) {
-        uint8_t* row = out + op * ROW;
+        uint8_t* row = out + op * row_len;
 #pragma unroll
         for (int i = 0; i < 10; i++) row[i] = live ? OID_PREFIX[i] : 0;
-        row[10] = live ? T::OID_LAST : 0;
+        row[10] = live ? oid_last : 0;
 #pragma unroll
-        for (int i = 0; i < T::DIGEST; i++) row[OID_LEN + i] = live ? dig[i] : 0;
+        for (int i = 0; i < MAX_DIGEST; i++)  // a truncated digest ends the row: nothing behind it is written
+            if (i < digest) row[OID_LEN + i] = live ? dig[i] : 0;
         if (bad) bad[op] = msg_bad ? 1 : 0;
         if (out_off) {
-            out_off[op] = (uint64_t)op * ROW;
-            if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * ROW;
+            out_off[op] = (uint64_t)op * row_len;
+            if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * row_len;
+        }
+    }
+}
+
+// One message per wave: block blockIdx.x hashes op blockIdx.x.  The lanes that hold a rate word load their own (lo, hi) of
+// each block -- the whole block in one wave-wide load -- and the digest leaves through the lanes of words 0 .. 7.
+template <int RATE>
+__global__ __launch_bounds__(64) void k_prehash_wave(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off,
+                                                     const uint8_t* __restrict__ ctxs, const uint64_t* __restrict__ ctx_off,
+                                                     uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
+                                                     uint8_t* __restrict__ bad, size_t n_ops, PhVar var) {
+    const int lane = threadIdx.x;
+    const size_t op = blockIdx.x;  // the launch has exactly n_ops blocks
+    const int digest = var.digest;
+    const size_t row_len = (size_t)OID_LEN + digest;
+    const uint32_t padb = var.padb;
+    const Coop2Lane c = mldsa::coop2_lane(lane);
+    const OpMsg o = check_op(msgs, msg_off, ctxs, ctx_off, op, n_ops);  // wave-uniform
+    const size_t blocks = o.live ? o.mlen / RATE + 1 : 0;                // the pad always fits in the last block
+
+    uint32_t v = 0;
+    const bool absorbs = c.active && c.word < RATE / 8;
+    for (size_t b = 0; b < blocks; b++) {
+        if (absorbs) {
+            const size_t pos = b * RATE + 8 * (size_t)c.word;
+            const uint32_t lo = padded_le32(o.mp, o.mlen, pos, padb);
+            uint32_t hi = padded_le32(o.mp, o.mlen, pos + 4, padb);
+            if (b == blocks - 1 && c.word == RATE / 8 - 1) hi ^= 0x80000000u;
+            v ^= mldsa::coop2_from_lohi(lo, hi, c);
+        }
+        mldsa::keccak_f1600_coop2(v, c);
+    }
+    uint32_t lo, hi;
+    mldsa::coop2_to_lohi(v, lane, lo, hi);  // a refused op never entered the loop: v = 0, an all-zero digest
+
+    uint8_t* row = out + op * row_len;
+    if (lane < 32 && c.active && c.word < 8) {  // lanes 0 .. 7: digest bytes 8 word .. 8 word + 7 (digest lengths are multiples of 4)
+        uint8_t* d = row + OID_LEN + 8 * c.word;
+        if (8 * c.word < digest) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) d[k] = (uint8_t)(lo >> (8 * k));
+        }
+        if (8 * c.word + 4 < digest) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) d[4 + k] = (uint8_t)(hi >> (8 * k));
+        }
+    } else if (lane >= 32 && lane < 32 + OID_LEN) {
+        const int i = lane - 32;
+        uint32_t b = var.oid_last;
+#pragma unroll
+        for (int k = 0; k < 10; k++) b = i == k ? OID_PREFIX[k] : b;
+        row[i] = o.live ? (uint8_t)b : 0;
+    } else if (lane == 63) {
+        if (bad) bad[op] = o.msg_bad ? 1 : 0;
+        if (out_off) {
+            out_off[op] = (uint64_t)op * row_len;
+            if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * row_len;
         }
     }
 }
@@ -231,18 +329,28 @@ size_t scratch_of(int ph, size_t n) {
 
 int launch_prehash(int ph, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off, uint8_t* out,
                    uint64_t* out_off, uint8_t* bad, size_t n_ops, hipStream_t s) {
-    const dim3 grid((unsigned)((n_ops + 63) / 64)), block(64);
-    switch (ph) {
-        case MLDSA_PH_SHA256:
-            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHA256>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
-            break;
-        case MLDSA_PH_SHA512:
-            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHA512>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
-            break;
-        default:
-            hipLaunchKernelGGL(k_prehash<MLDSA_PH_SHAKE128>, grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops);
-            break;
-    }
+    PhInfo info;
+    if (!mldsa_ph::ph_info(ph, &info)) return fail(MLDSA_ERR_PARAM, "k_prehash launch: unknown ph");
+    const bool wave = info.fam == FAM_KECCAK && n_ops <= (size_t)MLDSA_PH_COOP_MAX_OPS;
+    const dim3 grid((unsigned)(wave ? n_ops : (n_ops + 63) / 64)), block(64);
+    mldsa_ph::dispatch_instance(info, [&](auto fc, auto bc) {
+        constexpr int FAM = decltype(fc)::value, BLOCK = decltype(bc)::value;
+        if constexpr (FAM == FAM_KECCAK) {
+            if (wave) {
+                hipLaunchKernelGGL((k_prehash_wave<BLOCK>), grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops, info.var);
+                return;
+            }
+        }
+        // the reference's three have instances of their own (FixedVar); SHAKE128 is the only function at rate 168
+        if (ph == MLDSA_PH_SHA256 || ph == MLDSA_PH_SHA512 || ph == MLDSA_PH_SHAKE128) {
+            constexpr int PH = FAM == FAM_SHA2_32 ? MLDSA_PH_SHA256 : FAM == FAM_SHA2_64 ? MLDSA_PH_SHA512 : MLDSA_PH_SHAKE128;
+            if constexpr (FAM != FAM_KECCAK || BLOCK == 168)
+                hipLaunchKernelGGL((k_prehash<FAM, BLOCK, PH>), grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops, info.var);
+        } else {
+            if constexpr (FAM != FAM_KECCAK || BLOCK != 168)
+                hipLaunchKernelGGL((k_prehash<FAM, BLOCK, -1>), grid, block, 0, s, msgs, msg_off, ctxs, ctx_off, out, out_off, bad, n_ops, info.var);
+        }
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MLDSA_ERR_DEVICE, std::string("k_prehash launch: ") + hipGetErrorString(e));
     return MLDSA_OK;
@@ -294,12 +402,8 @@ int core_failed(const char* fn, int rc) {
 }
 
 int row_len_of(int ph) {
-    switch (ph) {
-        case MLDSA_PH_SHA256: return OID_LEN + 32;
-        case MLDSA_PH_SHA512: return OID_LEN + 64;
-        case MLDSA_PH_SHAKE128: return OID_LEN + 32;
-        default: return -1;
-    }
+    PhInfo info;
+    return ph_info(ph, &info) ? OID_LEN + info.var.digest : -1;
 }
 
 }  // namespace mldsa_ph

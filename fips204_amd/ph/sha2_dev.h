@@ -1,4 +1,5 @@
-// SHA-256 and SHA-512 compression functions for gfx950, one hash state per lane (FIPS 180-4 §6.2, §6.4).
+// SHA-256 and SHA-512 compression functions for gfx950, one hash state per lane (FIPS 180-4 §6.2, §6.4), and the initial
+// values of the six SHA-2 functions that run on them (SHA-224/256, SHA-384/512, SHA-512/224, SHA-512/256).
 //
 // The HashML-DSA pre-hash PH(M) (reference src/hashing.rs:317-354) runs one message per lane, 64 messages per wave,
 // like k_mu's SHAKE256 (csrc/kernels_codec.hip).  The state and the 16-word message schedule live in VGPRs; SHA-512's
@@ -46,9 +47,17 @@ struct Sha256State {
     uint32_t h[8];
 };
 
-__device__ __forceinline__ void sha256_init(Sha256State& s) {
-    s.h[0] = 0x6a09e667u; s.h[1] = 0xbb67ae85u; s.h[2] = 0x3c6ef372u; s.h[3] = 0xa54ff53au;
-    s.h[4] = 0x510e527fu; s.h[5] = 0x9b05688cu; s.h[6] = 0x1f83d9abu; s.h[7] = 0x5be0cd19u;
+// Initial values (FIPS 180-4 §5.3).  SHA-256 / SHA-512: fractional parts of the square roots of the first eight primes;
+// SHA-384: of the 9th-16th primes; SHA-224: the low 32 bits of SHA-384's.
+constexpr uint32_t IV256_SHA256[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+constexpr uint32_t IV256_SHA224[8] = {0xc1059ed8u, 0x367cd507u, 0x3070dd17u, 0xf70e5939u, 0xffc00b31u, 0x68581511u, 0x64f98fa7u, 0xbefa4fa4u};
+
+// iv: 0 = SHA-256, 1 = SHA-224 (PhVar::iv)
+__device__ __forceinline__ void sha256_init(Sha256State& s, int iv) {
+    static_for<0, 8>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        s.h[i] = iv == 1 ? IV256_SHA224[i] : IV256_SHA256[i];
+    });
 }
 
 struct Sha256K {
@@ -119,11 +128,22 @@ struct Sha512State {
     U64 h[8];
 };
 
-__device__ __forceinline__ void sha512_init(Sha512State& s) {
-    s.h[0] = lit64(0x6a09e667f3bcc908ull); s.h[1] = lit64(0xbb67ae8584caa73bull);
-    s.h[2] = lit64(0x3c6ef372fe94f82bull); s.h[3] = lit64(0xa54ff53a5f1d36f1ull);
-    s.h[4] = lit64(0x510e527fade682d1ull); s.h[5] = lit64(0x9b05688c2b3e6c1full);
-    s.h[6] = lit64(0x1f83d9abfb41bd6bull); s.h[7] = lit64(0x5be0cd19137e2179ull);
+constexpr uint64_t IV512_SHA512[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                      0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+constexpr uint64_t IV512_SHA384[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull, 0x9159015a3070dd17ull, 0x152fecd8f70e5939ull,
+                                      0x67332667ffc00b31ull, 0x8eb44a8768581511ull, 0xdb0c2e0d64f98fa7ull, 0x47b5481dbefa4fa4ull};
+// SHA-512/t (§5.3.6): SHA-512 started from IV512_SHA512 ^ a5a5...a5 over the ASCII string "SHA-512/224" / "SHA-512/256"
+constexpr uint64_t IV512_SHA512_224[8] = {0x8c3d37c819544da2ull, 0x73e1996689dcd4d6ull, 0x1dfab7ae32ff9c82ull, 0x679dd514582f9fcfull,
+                                          0x0f6d2b697bd44da8ull, 0x77e36f7304c48942ull, 0x3f9d85a86a1d36c8ull, 0x1112e6ad91d692a1ull};
+constexpr uint64_t IV512_SHA512_256[8] = {0x22312194fc2bf72cull, 0x9f555fa3c84c64c2ull, 0x2393b86b6f53b151ull, 0x963877195940eabdull,
+                                          0x96283ee2a88effe3ull, 0xbe5e1e2553863992ull, 0x2b0199fc2c85b8aaull, 0x0eb72ddc81c52ca2ull};
+
+// iv: 0 = SHA-512, 1 = SHA-384, 2 = SHA-512/224, 3 = SHA-512/256 (PhVar::iv)
+__device__ __forceinline__ void sha512_init(Sha512State& s, int iv) {
+    static_for<0, 8>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        s.h[i] = lit64(iv == 1 ? IV512_SHA384[i] : iv == 2 ? IV512_SHA512_224[i] : iv == 3 ? IV512_SHA512_256[i] : IV512_SHA512[i]);
+    });
 }
 
 struct Sha512K {

@@ -6,9 +6,11 @@
 // store each word of their states as one coalesced access.
 //   word 0, 1   bytes absorbed so far (64-bit count; count mod BLOCK bytes are buffered)
 //   word 2      bad: a piece pair of this op was malformed (sticky)
-//   SHA-256     8 chaining words, then the partial block as 16 little-endian dwords of message bytes
-//   SHA-512     8 chaining words as (lo, hi) pairs, then the partial block as 32 dwords
-//   SHAKE128    the 25 lanes of the sponge as (lo, hi) pairs; a partial block is XORed straight into them
+//   SHA-224/256           8 chaining words, then the partial block as 16 little-endian dwords of message bytes
+//   SHA-384/512, 512/t    8 chaining words as (lo, hi) pairs, then the partial block as 32 dwords
+//   SHA-3, SHAKE          the 25 lanes of the sponge as (lo, hi) pairs; a partial block is XORed straight into them
+// One instance of each kernel per family (SHA-2 with 32-bit words, SHA-2 with 64-bit words, Keccak): the functions of a family
+// differ by the PhVar argument -- Keccak's rate included -- and share its state layout.
 // The partial block never sits in a per-lane array (a run-time byte position into registers would land in scratch
 // memory): it lies in the state as dwords of message bytes.  A piece that completes it is first appended to it there (byte
 // and dword stores of the lane into its own words), then the 16 / 32 dwords are hashed as iteration 0 of the block loop;
@@ -33,25 +35,31 @@ using mldsa_ph::bswap32;
 using mldsa_ph::fail;
 using mldsa_ph::OID_LEN;
 using mldsa_ph::OID_PREFIX;
-using mldsa_ph::PhTraits;
+using mldsa_ph::FAM_KECCAK;
+using mldsa_ph::FAM_SHA2_32;
+using mldsa_ph::FAM_SHA2_64;
+using mldsa_ph::FamTraits;
+using mldsa_ph::PhInfo;
+using mldsa_ph::PhVar;
 using mldsa_ph::row_len_of;
 using mldsa_ph::static_for;
 
 constexpr int W_CNT = 0, W_BAD = 2, W_H = 3;
 
-template <int PH> struct StTraits;
-template <> struct StTraits<MLDSA_PH_SHA256> { static constexpr int H_WORDS = 8, BUF_WORDS = 16; };
-template <> struct StTraits<MLDSA_PH_SHA512> { static constexpr int H_WORDS = 16, BUF_WORDS = 32; };
-template <> struct StTraits<MLDSA_PH_SHAKE128> { static constexpr int H_WORDS = 50, BUF_WORDS = 0; };
-template <int PH> constexpr int W_BUF = W_H + StTraits<PH>::H_WORDS;
-template <int PH> constexpr int ST_WORDS = W_H + StTraits<PH>::H_WORDS + StTraits<PH>::BUF_WORDS;
+template <int FAM> struct StTraits;
+template <> struct StTraits<FAM_SHA2_32> { static constexpr int H_WORDS = 8, BUF_WORDS = 16; };
+template <> struct StTraits<FAM_SHA2_64> { static constexpr int H_WORDS = 16, BUF_WORDS = 32; };
+template <> struct StTraits<FAM_KECCAK> { static constexpr int H_WORDS = 50, BUF_WORDS = 0; };  // every rate: the whole sponge
+template <int FAM> constexpr int W_BUF = W_H + StTraits<FAM>::H_WORDS;
+template <int FAM> constexpr int ST_WORDS = W_H + StTraits<FAM>::H_WORDS + StTraits<FAM>::BUF_WORDS;
 
 int state_words(int ph) {
-    switch (ph) {
-        case MLDSA_PH_SHA256: return ST_WORDS<MLDSA_PH_SHA256>;
-        case MLDSA_PH_SHA512: return ST_WORDS<MLDSA_PH_SHA512>;
-        case MLDSA_PH_SHAKE128: return ST_WORDS<MLDSA_PH_SHAKE128>;
-        default: return -1;
+    PhInfo info;
+    if (!mldsa_ph::ph_info(ph, &info)) return -1;
+    switch (info.fam) {
+        case FAM_SHA2_32: return ST_WORDS<FAM_SHA2_32>;
+        case FAM_SHA2_64: return ST_WORDS<FAM_SHA2_64>;
+        default: return ST_WORDS<FAM_KECCAK>;
     }
 }
 
@@ -148,8 +156,8 @@ __device__ __forceinline__ size_t wave_max(size_t v) {
     return v;
 }
 
-template <int PH>
-__global__ __launch_bounds__(64) void k_ph_init(uint32_t* __restrict__ st, size_t n_ops) {
+template <int FAM>
+__global__ __launch_bounds__(64) void k_ph_init(uint32_t* __restrict__ st, size_t n_ops, PhVar var) {
     const size_t op = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (op >= n_ops) return;
     uint32_t* sp = st + op;
@@ -157,13 +165,13 @@ __global__ __launch_bounds__(64) void k_ph_init(uint32_t* __restrict__ st, size_
     sp[W_CNT * S] = 0;
     sp[(W_CNT + 1) * S] = 0;
     sp[W_BAD * S] = 0;
-    if constexpr (PH == MLDSA_PH_SHA256) {
+    if constexpr (FAM == FAM_SHA2_32) {
         mldsa_ph::Sha256State h;
-        mldsa_ph::sha256_init(h);
+        mldsa_ph::sha256_init(h, var.iv);
         store_h(h, sp, S);
-    } else if constexpr (PH == MLDSA_PH_SHA512) {
+    } else if constexpr (FAM == FAM_SHA2_64) {
         mldsa_ph::Sha512State h;
-        mldsa_ph::sha512_init(h);
+        mldsa_ph::sha512_init(h, var.iv);
         store_h(h, sp, S);
     } else {
 #pragma unroll
@@ -171,12 +179,11 @@ __global__ __launch_bounds__(64) void k_ph_init(uint32_t* __restrict__ st, size_
     }
 }
 
-template <int PH>
-__global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, const uint8_t* __restrict__ pieces,
-                                                  const uint64_t* __restrict__ off, size_t n_ops, size_t first, size_t count,
-                                                  uint64_t win_lo, uint64_t win_hi, uint64_t sub) {
-    using T = PhTraits<PH>;
-    constexpr int B = T::BLOCK;
+// the update of one lane's op for block size / rate B, a compile-time constant (k_ph_update below)
+template <int FAM, int B>
+__device__ __forceinline__ void update_body(uint32_t* __restrict__ st, const uint8_t* __restrict__ pieces,
+                                            const uint64_t* __restrict__ off, size_t n_ops, size_t first, size_t count,
+                                            uint64_t win_lo, uint64_t win_hi, uint64_t sub) {
     const size_t idx = (size_t)blockIdx.x * 64 + threadIdx.x;
     const size_t S = n_ops;
     uint32_t* sp = st;
@@ -207,7 +214,8 @@ __global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, con
     }
     const bool active = plen > 0;
 
-    if constexpr (PH == MLDSA_PH_SHAKE128) {
+    if constexpr (FAM == FAM_KECCAK) {
+        constexpr int RW = B / 8;  // 64-bit words of the rate
         // iterations of this lane: [the bytes that continue a partial block] [whole blocks] [the bytes left over]
         const bool head = active && fill > 0;
         const int take0 = head ? (int)((size_t)(B - fill) < plen ? (size_t)(B - fill) : plen) : 0;
@@ -226,13 +234,13 @@ __global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, con
                 const int o = is_head ? fill : 0;
                 const int take = is_head ? take0 : j < nblk ? B : rem;
                 if (take == B) {
-                    static_for<0, 21>([&](auto wc) {
+                    static_for<0, RW>([&](auto wc) {
                         constexpr int W = decltype(wc)::value;
                         ks.lo[W] ^= load_le32(src + 8 * W);
                         ks.hi[W] ^= load_le32(src + 8 * W + 4);
                     });
                 } else {
-                    static_for<0, 21>([&](auto wc) {
+                    static_for<0, RW>([&](auto wc) {
                         constexpr int W = decltype(wc)::value;
                         ks.lo[W] ^= window_le32(src, o, take, 8 * W);
                         ks.hi[W] ^= window_le32(src, o, take, 8 * W + 4);
@@ -251,9 +259,9 @@ __global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, con
         const size_t my_iters = (head ? 1 : 0) + nblk;
         const size_t max_iters = wave_max(my_iters);
         const uint8_t* body = mp + take0;
-        uint32_t* buf0 = sp + (size_t)W_BUF<PH> * S;
+        uint32_t* buf0 = sp + (size_t)W_BUF<FAM> * S;
         if (head) buf_append(buf0, S, fill, mp, take0);
-        if constexpr (PH == MLDSA_PH_SHA256) {
+        if constexpr (FAM == FAM_SHA2_32) {
             mldsa_ph::Sha256State h;
             if (my_iters) load_h(h, sp, S);
             for (size_t b = 0; b < max_iters; b++) {
@@ -303,12 +311,34 @@ __global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, con
     }
 }
 
-template <int PH>
+// One kernel per family.  Keccak's five rates are five inlined copies of the body behind a wave-uniform switch: with the rate
+// as a run-time bound the absorbing loop's 42 guarded dwords cost 4 spilled SGPRs (38 unguarded).
+template <int FAM>
+__global__ __launch_bounds__(64) void k_ph_update(uint32_t* __restrict__ st, const uint8_t* __restrict__ pieces,
+                                                  const uint64_t* __restrict__ off, size_t n_ops, size_t first, size_t count,
+                                                  uint64_t win_lo, uint64_t win_hi, uint64_t sub, PhVar var) {
+    if constexpr (FAM == FAM_SHA2_32) {
+        update_body<FAM, 64>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub);
+    } else if constexpr (FAM == FAM_SHA2_64) {
+        update_body<FAM, 128>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub);
+    } else {
+        switch (var.block) {
+            case 168: update_body<FAM, 168>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub); break;
+            case 144: update_body<FAM, 144>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub); break;
+            case 136: update_body<FAM, 136>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub); break;
+            case 104: update_body<FAM, 104>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub); break;
+            default: update_body<FAM, 72>(st, pieces, off, n_ops, first, count, win_lo, win_hi, sub); break;
+        }
+    }
+}
+
+template <int FAM>
 __global__ __launch_bounds__(64) void k_ph_final(const uint32_t* __restrict__ st, uint8_t* __restrict__ out,
-                                                 uint64_t* __restrict__ out_off, uint8_t* __restrict__ bad, size_t n_ops) {
-    using T = PhTraits<PH>;
-    constexpr int B = T::BLOCK;
-    constexpr int ROW = OID_LEN + T::DIGEST;
+                                                 uint64_t* __restrict__ out_off, uint8_t* __restrict__ bad, size_t n_ops, PhVar var) {
+    using T = FamTraits<FAM, FAM == FAM_SHA2_32 ? 64 : FAM == FAM_SHA2_64 ? 128 : 168>;  // TAIL and MAX_DIGEST: any rate's
+    const int B = FAM == FAM_SHA2_32 ? 64 : FAM == FAM_SHA2_64 ? 128 : (int)var.block;
+    const int digest = var.digest;
+    const size_t row_len = (size_t)OID_LEN + digest;
     const size_t op = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (op >= n_ops) return;
     const size_t S = n_ops;
@@ -316,10 +346,10 @@ __global__ __launch_bounds__(64) void k_ph_final(const uint32_t* __restrict__ st
     const uint64_t cnt = ((uint64_t)sp[(W_CNT + 1) * S] << 32) | sp[W_CNT * S];
     const bool is_bad = sp[W_BAD * S] != 0;
     const int fill = (int)(cnt % B);
-    const uint32_t* buf0 = sp + (size_t)W_BUF<PH> * S;
+    const uint32_t* buf0 = sp + (size_t)W_BUF<FAM> * S;
 
-    uint8_t dig[T::DIGEST];
-    if constexpr (PH == MLDSA_PH_SHA256) {
+    uint8_t dig[T::MAX_DIGEST];
+    if constexpr (FAM == FAM_SHA2_32) {
         mldsa_ph::Sha256State h;
         load_h(h, sp, S);
         const int blocks = fill + T::TAIL > B ? 2 : 1;
@@ -340,7 +370,7 @@ __global__ __launch_bounds__(64) void k_ph_final(const uint32_t* __restrict__ st
         for (int i = 0; i < 8; i++)
 #pragma unroll
             for (int k = 0; k < 4; k++) dig[4 * i + k] = (uint8_t)(h.h[i] >> (24 - 8 * k));
-    } else if constexpr (PH == MLDSA_PH_SHA512) {
+    } else if constexpr (FAM == FAM_SHA2_64) {
         mldsa_ph::Sha512State h;
         load_h(h, sp, S);
         const int blocks = fill + T::TAIL > B ? 2 : 1;
@@ -370,16 +400,17 @@ __global__ __launch_bounds__(64) void k_ph_final(const uint32_t* __restrict__ st
     } else {
         KeccakState ks;
         load_h(ks, sp, S);
-        const uint32_t pad = 0x1Fu << (8 * (fill & 3));
-        static_for<0, 21>([&](auto wc) {  // the pad byte at `fill`
+        const int rw = B >> 3;
+        const uint32_t pad = (uint32_t)var.padb << (8 * (fill & 3));
+        static_for<0, 21>([&](auto wc) {  // the pad byte at `fill` (< rate), and 0x80 in the last byte of this rate's block
             constexpr int W = decltype(wc)::value;
             if ((fill >> 2) == 2 * W) ks.lo[W] ^= pad;
             if ((fill >> 2) == 2 * W + 1) ks.hi[W] ^= pad;
+            if (W == rw - 1) ks.hi[W] ^= 0x80000000u;
         });
-        ks.hi[20] ^= 0x80000000u;  // last byte of the rate block
         mldsa::keccak_f1600(ks);
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 8; i++)
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 dig[8 * i + k] = (uint8_t)(ks.lo[i] >> (8 * k));
@@ -388,16 +419,17 @@ __global__ __launch_bounds__(64) void k_ph_final(const uint32_t* __restrict__ st
     }
 
     const bool live = !is_bad;
-    uint8_t* row = out + op * ROW;
+    uint8_t* row = out + op * row_len;
 #pragma unroll
     for (int i = 0; i < 10; i++) row[i] = live ? OID_PREFIX[i] : 0;
-    row[10] = live ? T::OID_LAST : 0;
+    row[10] = live ? var.oid_last : 0;
 #pragma unroll
-    for (int i = 0; i < T::DIGEST; i++) row[OID_LEN + i] = live ? dig[i] : 0;
+    for (int i = 0; i < T::MAX_DIGEST; i++)  // a truncated digest ends the row: nothing behind it is written
+        if (i < digest) row[OID_LEN + i] = live ? dig[i] : 0;
     if (bad) bad[op] = is_bad ? 1 : 0;
     if (out_off) {
-        out_off[op] = (uint64_t)op * ROW;
-        if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * ROW;
+        out_off[op] = (uint64_t)op * row_len;
+        if (op == n_ops - 1) out_off[n_ops] = (uint64_t)n_ops * row_len;
     }
 }
 
@@ -434,39 +466,45 @@ size_t state_bytes_of(int ph, size_t n_ops) {
 }
 
 int launch_init(int ph, uint32_t* state, size_t n_ops, hipStream_t s) {
+    PhInfo info;
+    if (!ph_info(ph, &info)) return fail(MLDSA_ERR_PARAM, "k_ph_init launch: unknown ph");
     const dim3 grid((unsigned)((n_ops + 63) / 64)), block(64);
-    switch (ph) {
-        case MLDSA_PH_SHA256: hipLaunchKernelGGL(k_ph_init<MLDSA_PH_SHA256>, grid, block, 0, s, state, n_ops); break;
-        case MLDSA_PH_SHA512: hipLaunchKernelGGL(k_ph_init<MLDSA_PH_SHA512>, grid, block, 0, s, state, n_ops); break;
-        default: hipLaunchKernelGGL(k_ph_init<MLDSA_PH_SHAKE128>, grid, block, 0, s, state, n_ops); break;
+    switch (info.fam) {
+        case FAM_SHA2_32: hipLaunchKernelGGL(k_ph_init<FAM_SHA2_32>, grid, block, 0, s, state, n_ops, info.var); break;
+        case FAM_SHA2_64: hipLaunchKernelGGL(k_ph_init<FAM_SHA2_64>, grid, block, 0, s, state, n_ops, info.var); break;
+        default: hipLaunchKernelGGL(k_ph_init<FAM_KECCAK>, grid, block, 0, s, state, n_ops, info.var); break;
     }
     return launched("k_ph_init");
 }
 
 int launch_update(int ph, uint32_t* state, const uint8_t* pieces, const uint64_t* off, size_t n_ops, size_t first, size_t count,
                   uint64_t win_lo, uint64_t win_hi, uint64_t sub, hipStream_t s) {
+    PhInfo info;
+    if (!ph_info(ph, &info)) return fail(MLDSA_ERR_PARAM, "k_ph_update launch: unknown ph");
     if (count == 0) return MLDSA_OK;
     const dim3 grid((unsigned)((count + 63) / 64)), block(64);
-    switch (ph) {
-        case MLDSA_PH_SHA256:
-            hipLaunchKernelGGL(k_ph_update<MLDSA_PH_SHA256>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub);
+    switch (info.fam) {
+        case FAM_SHA2_32:
+            hipLaunchKernelGGL(k_ph_update<FAM_SHA2_32>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub, info.var);
             break;
-        case MLDSA_PH_SHA512:
-            hipLaunchKernelGGL(k_ph_update<MLDSA_PH_SHA512>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub);
+        case FAM_SHA2_64:
+            hipLaunchKernelGGL(k_ph_update<FAM_SHA2_64>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub, info.var);
             break;
         default:
-            hipLaunchKernelGGL(k_ph_update<MLDSA_PH_SHAKE128>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub);
+            hipLaunchKernelGGL(k_ph_update<FAM_KECCAK>, grid, block, 0, s, state, pieces, off, n_ops, first, count, win_lo, win_hi, sub, info.var);
             break;
     }
     return launched("k_ph_update");
 }
 
 int launch_final(int ph, const uint32_t* state, uint8_t* out, uint64_t* out_off, uint8_t* bad, size_t n_ops, hipStream_t s) {
+    PhInfo info;
+    if (!ph_info(ph, &info)) return fail(MLDSA_ERR_PARAM, "k_ph_final launch: unknown ph");
     const dim3 grid((unsigned)((n_ops + 63) / 64)), block(64);
-    switch (ph) {
-        case MLDSA_PH_SHA256: hipLaunchKernelGGL(k_ph_final<MLDSA_PH_SHA256>, grid, block, 0, s, state, out, out_off, bad, n_ops); break;
-        case MLDSA_PH_SHA512: hipLaunchKernelGGL(k_ph_final<MLDSA_PH_SHA512>, grid, block, 0, s, state, out, out_off, bad, n_ops); break;
-        default: hipLaunchKernelGGL(k_ph_final<MLDSA_PH_SHAKE128>, grid, block, 0, s, state, out, out_off, bad, n_ops); break;
+    switch (info.fam) {
+        case FAM_SHA2_32: hipLaunchKernelGGL(k_ph_final<FAM_SHA2_32>, grid, block, 0, s, state, out, out_off, bad, n_ops, info.var); break;
+        case FAM_SHA2_64: hipLaunchKernelGGL(k_ph_final<FAM_SHA2_64>, grid, block, 0, s, state, out, out_off, bad, n_ops, info.var); break;
+        default: hipLaunchKernelGGL(k_ph_final<FAM_KECCAK>, grid, block, 0, s, state, out, out_off, bad, n_ops, info.var); break;
     }
     return launched("k_ph_final");
 }

@@ -1,7 +1,8 @@
 /* mldsa_ph.h -- HashML-DSA with the pre-hash on the GPU (libmldsa_ph.so).
  *
  * A front-end library layered on the C ABI of include/mldsa_hip.h.  It computes PH(M) -- SHA-256, SHA-512 or
- * SHAKE128 of each raw message, the reference's hash_message (src/hashing.rs:316-354) -- in one kernel, one
+ * SHAKE128 of each raw message, the reference's hash_message (src/hashing.rs:316-354), or one of the nine other
+ * functions of the NIST hash OID arc (MLDSA_PH_* below) -- in one kernel, one
  * message per lane, writes OID || PH(M) for every operation into caller-provided device scratch, and then calls
  * mldsa_verify / mldsa_verify_pk / mldsa_sign with MLDSA_MODE_PREHASH on the same stream.  It reaches the core
  * only through the core's public entry points, so every core call's behaviour is the core's.
@@ -44,11 +45,34 @@ extern "C" {
 #define MLDSA_PH_SHA256 0   /* OID 2.16.840.1.101.3.4.2.1,  32-byte digest (hashing.rs:319-329) */
 #define MLDSA_PH_SHA512 1   /* OID 2.16.840.1.101.3.4.2.3,  64-byte digest (hashing.rs:330-340) */
 #define MLDSA_PH_SHAKE128 2 /* OID 2.16.840.1.101.3.4.2.11, 32 bytes of output (hashing.rs:341-352) */
+/* The other functions of the NIST arc 2.16.840.1.101.3.4.2.* (FIPS 204 §5.4 allows any approved hash or XOF): code = 16 + the
+ * last OID arc.  0, 1, 2 keep their meaning; 3-15 and every other value are unknown.  The library does not police FIPS 204's
+ * strength recommendation (e.g. SHA-224 with ML-DSA-87), as the reference does not for SHA-256. */
+#define MLDSA_PH_SHA384 18     /* ...4.2.2,  48-byte digest */
+#define MLDSA_PH_SHA224 20     /* ...4.2.4,  28-byte digest */
+#define MLDSA_PH_SHA512_224 21 /* ...4.2.5,  28-byte digest */
+#define MLDSA_PH_SHA512_256 22 /* ...4.2.6,  32-byte digest */
+#define MLDSA_PH_SHA3_224 23   /* ...4.2.7,  28-byte digest */
+#define MLDSA_PH_SHA3_256 24   /* ...4.2.8,  32-byte digest */
+#define MLDSA_PH_SHA3_384 25   /* ...4.2.9,  48-byte digest */
+#define MLDSA_PH_SHA3_512 26   /* ...4.2.10, 64-byte digest */
+#define MLDSA_PH_SHAKE256 28   /* ...4.2.12, 64 bytes of output (FIPS 204: 512 bits) */
+
+/* One-shot calls (mldsa_prehash, mldsa_hash_verify, mldsa_hash_verify_pk, mldsa_hash_sign) of at most this many operations
+ * run the six Keccak-family functions one message per WAVE on the core's cooperative sponge instead of one per lane; rows,
+ * refusals and the offset table are the same bytes in either form.  A compile-time constant of the library (0: never).
+ * Measured (profiles/prehash_fips_list_bench.jsonl, "prehash_small_call", SHAKE256 / SHA3-512 / SHAKE128 at 1 KiB and 16 KiB,
+ * n = 1 ... 4096): the wave form's median latency of mldsa_prehash and of mldsa_hash_verify is below the lane form's by more
+ * than the lane form's p10-p90 spread at every n measured; 4096 is the largest of them (there: 68 against 94 us at 1 KiB). */
+#ifndef MLDSA_PH_COOP_MAX_OPS
+#define MLDSA_PH_COOP_MAX_OPS 4096
+#endif
 
 int mldsa_ph_abi_version(void);
 /* message of the last failed call of this thread; carries the core's message when a core call failed */
 const char *mldsa_ph_last_error(void);
-/* 43 / 75 / 43 = 11-byte DER OID + digest; negative for an unknown ph */
+/* 11-byte DER OID + digest: 43 / 75 / 43 for the codes 0 / 1 / 2, 39 / 43 / 59 / 75 for 28- / 32- / 48- / 64-byte digests;
+ * negative for an unknown ph */
 int mldsa_ph_row_len(int ph);
 /* device scratch the op-level calls need for n_ops operations: 8 (n_ops + 1) + n_ops row_len + n_ops bytes;
  * 0 for an unknown ph (or a size that does not fit a size_t) */
@@ -113,7 +137,7 @@ int mldsa_ph_final(mldsa_ctx *ctx, int ph, void *state, size_t state_bytes, uint
  *   positions -- a message may span any number of chunks, a chunk may hold thousands of messages -- and chunk i + 1 is
  *   uploaded while mldsa_ph_update runs on chunk i, for the ops that have bytes in it.  The device memory of a call is
  *   2 staging_bytes + states + rows + one offset table, whatever the size of the messages.  After mldsa_ph_final the rows
- *   (43 / 75 bytes per op) are brought to the host and mldsa_verify_host / mldsa_sign_host run in MLDSA_MODE_PREHASH:
+ *   (39 ... 75 bytes per op) are brought to the host and mldsa_verify_host / mldsa_sign_host run in MLDSA_MODE_PREHASH:
  *   verdicts, signatures, statuses and per-op refusals are the core's.
  * Refusal rules are those of the core's *_host calls: both offset tables are checked first (mldsa_check_offsets) and a
  *   malformed table, or a msg_off that names bytes of a NULL msgs, fails the whole call with MLDSA_ERR_PARAM before a

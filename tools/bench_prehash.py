@@ -22,6 +22,13 @@ Ceiling GB/s = SIMDs x clock x 64 lanes x block bytes / cycles per block, for on
   staging_sweep    mldsa_hash_verify_host at --sweep-len bytes per message for staging chunks of --sweep-mib MiB
 
     python tools/bench_prehash.py --stream >> profiles/prehash_stream_bench.jsonl
+
+--phs takes any of the twelve Ph names of fips204_amd.ml_dsa.  --lib PATH measures another build of libmldsa_ph.so (the parent
+commit's, or one compiled with -DMLDSA_PH_COOP_MAX_OPS=0) through the same Python, and --label TEXT tags every line with it.
+--small measures the small-call latency instead: mldsa_prehash and hash_verify_device for --ns operations, the host clock around
+a call that ends in a synchronise, --calls calls after warm-up, median and percentiles (one JSON line per PH, length and n).
+
+    python tools/bench_prehash.py --small --phs SHAKE256,SHA3_512 --lens 1024,16384 --label wave >> profiles/prehash_fips_list_bench.jsonl
 """
 import argparse
 import json
@@ -34,15 +41,19 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 SIMDS, CLOCK_GHZ = 256 * 4, 2.4
-BLOCK_BYTES = {"SHA256": 64, "SHA512": 128, "SHAKE128": 168}
+BLOCK_BYTES = {"SHA256": 64, "SHA224": 64, "SHA512": 128, "SHA384": 128, "SHA512_224": 128, "SHA512_256": 128,
+               "SHAKE128": 168, "SHA3_224": 144, "SHA3_256": 136, "SHAKE256": 136, "SHA3_384": 104, "SHA3_512": 72}
 # instruction classes of one block of one wave, from the disassembly of k_prehash<PH> (counts of the compression / permutation loop)
 MIX = {
     "SHA256": {"v_alignbit_b32": 576, "v_bitop3_b32": 352, "v_add3_u32": 241, "v_add_u32": 119, "v_lshrrev_b32": 96, "v_perm_b32": 16},
     "SHA512": {"v_alignbit_b32": 1570, "v_bitop3_b32": 896, "v_lshl_add_u64": 768, "v_add3_u32": 448, "v_mov_b32": 992,
                "v_add_u32": 247, "v_lshrrev_b32": 128, "v_perm_b32": 32},
-    # 24 rounds of csrc/keccak.h (70 bitop3 + 58 alignbit + 62 xor per round) + the 42 absorbing XORs
-    "SHAKE128": {"v_bitop3_b32": 24 * 70, "v_alignbit_b32": 24 * 58, "v_xor_b32": 24 * 62 + 42},
 }
+# the functions of a family run the same compression loop: only initial value and digest length differ
+MIX.update({"SHA224": MIX["SHA256"], "SHA384": MIX["SHA512"], "SHA512_224": MIX["SHA512"], "SHA512_256": MIX["SHA512"]})
+# Keccak family: 24 rounds of csrc/keccak.h (70 bitop3 + 58 alignbit + 62 xor per round) + one absorbing XOR per dword of the rate
+MIX.update({ph: {"v_bitop3_b32": 24 * 70, "v_alignbit_b32": 24 * 58, "v_xor_b32": 24 * 62 + BLOCK_BYTES[ph] // 4}
+            for ph in ("SHAKE128", "SHA3_224", "SHA3_256", "SHAKE256", "SHA3_384", "SHA3_512")})
 
 
 def issue_costs(path):
@@ -215,6 +226,58 @@ def stream_legs(args):
         m.lib.mldsa_host_free(hs)
 
 
+def small_legs(args):
+    """small-call latency: the host clock around one call that ends in a synchronise"""
+    import numpy as np
+    import torch
+
+    from fips204_amd.ml_dsa import MlDsa
+
+    m = MlDsa(65)
+    nk = 16
+    pk, sk = m.keygen_from_seed([bytes([i]) * 32 for i in range(nk)])
+    pks, sks = m.public_keys_from_bytes(pk), m.private_keys_from_bytes(sk)
+
+    def latency(fn):
+        for _ in range(args.warmup_calls):
+            fn()
+        t = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e6)
+        q = np.percentile(t, [50, 10, 25, 75, 90])
+        return {"median_us": round(float(q[0]), 1), "p10_us": round(float(q[1]), 1), "p25_us": round(float(q[2]), 1),
+                "p75_us": round(float(q[3]), 1), "p90_us": round(float(q[4]), 1), "min_us": round(float(min(t)), 1),
+                "max_us": round(float(max(t)), 1)}
+
+    for ph in args.phs.split(","):
+        for L in [int(x) for x in args.lens.split(",")]:
+            for n in [int(x) for x in args.ns.split(",")]:
+                g = torch.Generator(device="cuda").manual_seed(L)
+                buf = torch.randint(0, 256, (n * L + 16,), dtype=torch.uint8, device="cuda", generator=g)
+                off = torch.arange(n + 1, dtype=torch.int64, device="cuda") * L
+                kidx = torch.from_numpy((np.arange(n) % nk).astype(np.int32)).cuda()
+                rnd = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+                sigs = torch.empty((n, m.SIG_LEN), dtype=torch.uint8, device="cuda")
+                ok = torch.empty(n, dtype=torch.uint8, device="cuda")
+                m.hash_sign_device(sks, buf, off, rnd, sigs, n, ph, key_idx=kidx)
+
+                def call_prehash():
+                    m.prehash_device(buf, off, n, ph)
+                    torch.cuda.synchronize()
+
+                def call_verify():
+                    m.hash_verify_device(pks, buf, off, sigs, ok, n, ph, key_idx=kidx)
+                    torch.cuda.synchronize()
+
+                rec = {"workload": "prehash_small_call", "label": args.label, "set": 65, "ph": ph, "n_ops": n, "msg_len": L,
+                       "calls": args.calls, "clock": "host perf_counter around call + synchronise",
+                       "prehash": latency(call_prehash), "hash_verify_device": latency(call_verify)}
+                assert bool(ok.all())
+                print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=65536)
@@ -229,9 +292,21 @@ def main():
     ap.add_argument("--legs", default="prehash_stream,hash_host,staging_sweep")
     ap.add_argument("--sweep-len", type=int, default=16384)
     ap.add_argument("--sweep-mib", default="1,4,16,64")
+    ap.add_argument("--lib", default="", help="measure this build of libmldsa_ph.so instead of the tree's")
+    ap.add_argument("--label", default="", help="copied into every JSON line")
+    ap.add_argument("--ops-lens", default="", help="message lengths at which the op-level and pure-mode calls are measured too (default: all)")
+    ap.add_argument("--small", action="store_true", help="small-call latency of mldsa_prehash and hash_verify_device instead")
+    ap.add_argument("--ns", default="1,8,64,256,1024,4096", help="--small: operations per call")
+    ap.add_argument("--calls", type=int, default=200, help="--small: timed calls per point")
+    ap.add_argument("--warmup-calls", type=int, default=20)
     args = ap.parse_args()
+    if args.lib:
+        from fips204_amd import _ph_lib
+        _ph_lib.LIB_PATH = os.path.abspath(args.lib)
     if args.stream:
         return stream_legs(args)
+    if args.small:
+        return small_legs(args)
 
     import numpy as np
     import torch
@@ -256,6 +331,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1) / steps  # ms
 
+    ops_lens = [int(x) for x in args.ops_lens.split(",")] if args.ops_lens else None
     points = [(n_, L, ph) for L in [int(x) for x in args.lens.split(",")] for ph in args.phs.split(",") for n_ in [args.n]]
     if args.big:
         points += [(args.big, 1024, ph) for ph in args.phs.split(",")]
@@ -269,15 +345,22 @@ def main():
         ok = torch.empty(n, dtype=torch.uint8, device="cuda")
         st = torch.empty(n, dtype=torch.int32, device="cuda")
         ph_ms = timed(lambda: m.prehash_device(buf, off, n, ph), args.steps, args.warmup)
+        gbs = n * L / (ph_ms * 1e-3) / 1e9
+        ceil_gbs, ceil = ceiling(ph, costs) if costs else (None, {"missing_issue_costs": "no ubench file"})
+        if ops_lens is not None and L not in ops_lens:
+            print(json.dumps({"workload": "prehash", "label": args.label, "set": 65, "ph": ph, "n_ops": n, "msg_len": L,
+                              "prehash_us": round(ph_ms * 1e3, 1), "prehash_GBs": round(gbs, 1),
+                              "prehash_fraction_of_ceiling": round(gbs / ceil_gbs, 3) if ceil_gbs else None, "ceiling": ceil}), flush=True)
+            del buf, sigs
+            torch.cuda.empty_cache()
+            continue
         hs_ms = timed(lambda: m.hash_sign_device(sks, buf, off, rnd, sigs, n, ph, key_idx=kidx, status=st), max(2, args.steps // 3), 1)
         assert int(st.min()) == 0
         hv_ms = timed(lambda: m.hash_verify_device(pks, buf, off, sigs, ok, n, ph, key_idx=kidx), args.steps, args.warmup)
         assert bool(ok.all())
         pv_ms = timed(lambda: m.verify_device(pks, buf, off, sigs, ok, n, key_idx=kidx), args.steps, args.warmup)
         ps_ms = timed(lambda: m.sign_device(sks, buf, off, rnd, sigs, n, key_idx=kidx, status=st), max(2, args.steps // 3), 1)
-        gbs = n * L / (ph_ms * 1e-3) / 1e9
-        ceil_gbs, ceil = ceiling(ph, costs) if costs else (None, {"missing_issue_costs": "no ubench file"})
-        rec = {"workload": "prehash", "set": 65, "ph": ph, "n_ops": n, "msg_len": L,
+        rec = {"workload": "prehash", "label": args.label, "set": 65, "ph": ph, "n_ops": n, "msg_len": L,
                "prehash_us": round(ph_ms * 1e3, 1), "prehash_GBs": round(gbs, 1),
                "prehash_fraction_of_ceiling": round(gbs / ceil_gbs, 3) if ceil_gbs else None,
                "hash_verify_device_ms": round(hv_ms, 3), "hash_sign_device_ms": round(hs_ms, 3),
