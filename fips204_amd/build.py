@@ -1,12 +1,16 @@
-"""Builds fips204_amd/csrc/libmldsa_hip.so (hipcc, --offload-arch=gfx950) in-tree, then the layered pre-hash library
-fips204_amd/ph/libmldsa_ph.so (include/mldsa_ph.h), which links the core and never rebuilds it."""
+"""Builds fips204_amd/csrc/libmldsa_hip.so (hipcc, --offload-arch=gfx950) in-tree, then the layered libraries, which link the
+core and never rebuild it: the pre-hash library fips204_amd/ph/libmldsa_ph.so (include/mldsa_ph.h) and the key-deduplication
+library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h)."""
 import os
 import subprocess
 
-CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+_HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libmldsa_hip.so")
-PH_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ph")
+PH_DIR = os.path.join(_HERE, "ph")
 PH_LIB = os.path.join(PH_DIR, "libmldsa_ph.so")
+KEYS_DIR = os.path.join(_HERE, "keys")
+KEYS_LIB = os.path.join(KEYS_DIR, "libmldsa_keys.so")
 
 
 def build(force=False, jobs=8):
@@ -16,11 +20,12 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    if force:
-        subprocess.check_call(["make", "-C", PH_DIR, "clean"], stdout=subprocess.DEVNULL)
-    subprocess.check_call(["make", "-C", PH_DIR, f"-j{jobs}"], stdout=subprocess.DEVNULL)
-    if not os.path.exists(PH_LIB):
-        raise RuntimeError(f"build did not produce {PH_LIB}")
+    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB)):
+        if force:
+            subprocess.check_call(["make", "-C", layer_dir, "clean"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", layer_dir, f"-j{jobs}"], stdout=subprocess.DEVNULL)
+        if not os.path.exists(layer_lib):
+            raise RuntimeError(f"build did not produce {layer_lib}")
     return LIB
 
 

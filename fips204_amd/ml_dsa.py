@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, _ph_lib
+from . import _keys_lib, _lib, _ph_lib
 from .hotpath import HotPath, N, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -223,8 +223,9 @@ class MlDsa:
             _stream(self.device)))
         return ok
 
-    def verify_pk(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, mode=MODE_PURE):
-        """PublicKey::try_from_bytes(pk)?.verify(message, sig, ctx) for a batch of wire-format keys (src/lib.rs:471-475, 364-380)"""
+    def verify_pk(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, mode=MODE_PURE, dedup=False):
+        """PublicKey::try_from_bytes(pk)?.verify(message, sig, ctx) for a batch of wire-format keys (src/lib.rs:471-475, 364-380).
+        dedup=True: through verify_pk_dedup_device (equal keys are found on the device and expanded once); same verdicts."""
         n_ops = len(messages)
         pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
         msg_buf, msg_off = _cat_with_offsets(messages, self.device)
@@ -236,9 +237,73 @@ class MlDsa:
             kidx = torch.as_tensor(kidx.view(np.int32)).to(self.device)
         sg = self._key_bytes(sigs, self.SIG_LEN, "sigs") if n_ops else torch.zeros((1, self.SIG_LEN), dtype=torch.uint8, device=self.device)
         ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
-        self.verify_pk_device(pk, msg_buf, msg_off, sg, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
+        if dedup:
+            self.verify_pk_dedup_device(pk, msg_buf, msg_off, sg, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
+        else:
+            self.verify_pk_device(pk, msg_buf, msg_off, sg, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
         torch.cuda.synchronize(self.device)
         return ok[:n_ops].cpu().numpy().astype(bool)
+
+    # ---- equal wire-format keys found on the device (include/mldsa_keys.h) ------------
+    @staticmethod
+    def _dedup_seed(seed):
+        seed = OsRng().fill_bytes(16) if seed is None else bytes(seed)
+        if len(seed) != 16:
+            raise ValueError("seed: 16 bytes expected")
+        return seed
+
+    def dedup_public_keys_device(self, pk_bytes, seed=None, hash_bits=64, table_rows=None):
+        """mldsa_keys_dedup: (row_of [n] int32, table [table_rows, PK_LEN] uint8, n_rows [1] int32), all on the device and
+        asynchronous on the current stream.  table[row_of[i]] == pk[i]; rows are numbered in order of first occurrence and n_rows
+        of them exist; the table holds the rows below table_rows (default: n, so every row).  seed: 16 bytes (None: from OsRng)."""
+        lib = _keys_lib.load()
+        pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
+        n = pk.shape[0]
+        rows = n if table_rows is None else int(table_rows)
+        row_of = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        table = torch.empty((max(rows, 1), self.PK_LEN), dtype=torch.uint8, device=self.device)
+        n_rows = torch.empty(1, dtype=torch.int32, device=self.device)
+        scratch = torch.empty(max(lib.mldsa_keys_dedup_scratch_bytes(self.pset, n), 16), dtype=torch.uint8, device=self.device)
+        _keys_lib.check(lib.mldsa_keys_dedup(self.hp._h, self.pset, _ptr(pk), n, self._dedup_seed(seed), hash_bits, _ptr(row_of),
+                                             _ptr(table) if rows else C.c_void_p(0), rows, _ptr(n_rows), _ptr(scratch), scratch.numel(),
+                                             _stream(self.device)))
+        return row_of[:n], table[:rows], n_rows
+
+    # Rows the cached route of verify_pk_dedup_device may build when the caller does not say: the largest number of distinct keys
+    # at which the route measured faster than mldsa_verify_pk at 65 536 ops (0.42 ... 0.52 of its time on the three sets; at 65 536
+    # distinct keys it loses 11 ... 14 %; profiles/keys_dedup_bench.jsonl).
+    DEDUP_MAX_CACHED_KEYS = 8192
+
+    def dedup_verify_scratch(self, n, max_cached_keys=None):
+        """device scratch for verify_pk_dedup_device calls of up to n ops and n keys, to be reused call after call on one stream"""
+        cap = min(self.DEDUP_MAX_CACHED_KEYS if max_cached_keys is None else int(max_cached_keys), n)
+        nb = _keys_lib.load().mldsa_keys_verify_scratch_bytes(self.pset, n, cap)
+        return torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+
+    def verify_pk_dedup_device(self, pk_bytes, msg_buf, msg_off, sigs, ok, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE,
+                               seed=None, hash_bits=64, max_cached_keys=None, info=None, scratch=None):
+        """mldsa_verify_pk_dedup: verify_pk_device's arguments and verdicts; equal keys are found on the device and the batch runs
+        on the table of distinct keys when there are at most max_cached_keys of them (None: DEDUP_MAX_CACHED_KEYS).  Waits once for
+        the current stream (the number of distinct keys decides the route).  info: a dict that receives n_rows and route.
+        scratch: the caller's own device scratch, a uint8 tensor from dedup_verify_scratch() (None: one is allocated for the call)."""
+        lib, null = _keys_lib.load(), C.c_void_p(0)
+        pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
+        n_keys = pk.shape[0]
+        n_dedup = n_keys if key_idx is not None else n_ops
+        cap = min(self.DEDUP_MAX_CACHED_KEYS if max_cached_keys is None else int(max_cached_keys), max(n_dedup, 0))
+        nb = lib.mldsa_keys_verify_scratch_bytes(self.pset, max(n_dedup, n_ops), cap)
+        if scratch is None:
+            scratch = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+        elif scratch.numel() < nb:
+            raise ValueError(f"scratch: {scratch.numel()} bytes, the call needs {nb}")
+        out = _keys_lib.KeysInfo()
+        _keys_lib.check(lib.mldsa_verify_pk_dedup(
+            self.hp._h, self.pset, mode, _ptr(pk), n_keys, _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
+            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(sigs), _ptr(ok), n_ops,
+            self._dedup_seed(seed), hash_bits, cap, _ptr(scratch), scratch.numel(), C.byref(out), _stream(self.device)))
+        if info is not None:
+            info["n_rows"], info["route"] = int(out.n_rows), ("cached" if out.route == _keys_lib.ROUTE_CACHED else "plain")
+        return ok
 
     # ---- SerDes (src/traits.rs:372-424; src/lib.rs:421-424, 471-475) ------------------
     def _key_bytes(self, keys, length, what):
