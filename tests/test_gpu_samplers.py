@@ -82,6 +82,9 @@ def test_expand_mask(hp, pset):
     kappa = rng.integers(0, 3000, n_ops).astype(np.uint16) * l
     kappa[0] = 0
     kappa[1] = 65535 - l + 1  # top of the u16 range without wrapping
+    # kappa + r is u16 arithmetic (hashing.rs:281-313): rows r >= 1, the last row only, and every row but the first two wrap to 0, 1, ...
+    kappa[2], kappa[3], kappa[4] = 65535, 65535 - l + 2, 65534
+    assert all(int(kappa[i]) + l - 1 > 65535 for i in (2, 3, 4)) and int(kappa[1]) + l - 1 == 65535
     kd = torch.from_numpy(kappa.view(np.int16)).cuda()
     got = host(hp.expand_mask(pset, devb(rho), kd))
     assert got.min() >= -gamma1 + 1 and got.max() <= gamma1
