@@ -1,6 +1,7 @@
 """Builds fips204_amd/csrc/libmldsa_hip.so (hipcc, --offload-arch=gfx950) in-tree, then the layered libraries, which link the
-core and never rebuild it: the pre-hash library fips204_amd/ph/libmldsa_ph.so (include/mldsa_ph.h) and the key-deduplication
-library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h)."""
+core and never rebuild it: the pre-hash library fips204_amd/ph/libmldsa_ph.so (include/mldsa_ph.h), the key-deduplication
+library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h) and the external-mu library fips204_amd/mu/libmldsa_mu.so
+(include/mldsa_mu.h)."""
 import os
 import subprocess
 
@@ -11,6 +12,8 @@ PH_DIR = os.path.join(_HERE, "ph")
 PH_LIB = os.path.join(PH_DIR, "libmldsa_ph.so")
 KEYS_DIR = os.path.join(_HERE, "keys")
 KEYS_LIB = os.path.join(KEYS_DIR, "libmldsa_keys.so")
+MU_DIR = os.path.join(_HERE, "mu")
+MU_LIB = os.path.join(MU_DIR, "libmldsa_mu.so")
 
 
 def build(force=False, jobs=8):
@@ -20,7 +23,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB)):
+    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB), (MU_DIR, MU_LIB)):
         if force:
             subprocess.check_call(["make", "-C", layer_dir, "clean"], stdout=subprocess.DEVNULL)
         subprocess.check_call(["make", "-C", layer_dir, f"-j{jobs}"], stdout=subprocess.DEVNULL)

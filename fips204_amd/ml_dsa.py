@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keys_lib, _lib, _ph_lib
+from . import _keys_lib, _lib, _mu_lib, _ph_lib
 from .hotpath import HotPath, N, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -72,6 +72,26 @@ def hash_message(message, ph):
     oid_last, name, xof_len, _ = _PH_TABLE[ph]
     h = hashlib.new(name, message)
     return _PH_OID + bytes([oid_last]) + (h.digest(xof_len) if xof_len else h.digest())
+
+
+def external_mu(tr, message, ctx=b"", mode=MODE_PURE):
+    """mu = H(BytesToBits(tr) || M', 64) on the host (FIPS 204 Algorithm 7 line 6): what a client that holds the message and the
+    key's 64-byte tr sends to a device that signs or verifies from mu (verify_mu / try_sign_mu_with_seed).  M' as the three modes
+    format it: MODE_INTERNAL M; MODE_PURE 0x00 | len(ctx) | ctx | M; MODE_PREHASH 0x01 | len(ctx) | ctx | M with M =
+    hash_message(...) = OID || PH(M)."""
+    import hashlib
+    tr, message, ctx = bytes(tr), bytes(message), bytes(ctx)
+    if len(tr) != 64:
+        raise ValueError("tr: 64 bytes expected")
+    if mode == MODE_INTERNAL:
+        m_prime = message
+    elif mode in (MODE_PURE, MODE_PREHASH):
+        if len(ctx) > 255:
+            raise ValueError("ctx too long (at most 255 bytes)")
+        m_prime = bytes([1 if mode == MODE_PREHASH else 0, len(ctx)]) + ctx + message
+    else:
+        raise ValueError("mode: MODE_PURE, MODE_INTERNAL or MODE_PREHASH")
+    return hashlib.shake_256(tr + m_prime).digest(64)
 
 
 def _cat_with_offsets(items, device):
@@ -654,6 +674,93 @@ class MlDsa:
             _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
             _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return sigs
+
+
+    # ---- externally computed mu (include/mldsa_mu.h) ---------------------------------------
+    def mu_device(self, tr, msg_buf, msg_off, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE):
+        """mldsa_mu_compute: (mu [n_ops, 64] uint8, mu_flag [n_ops] int32) on the device, asynchronous on the current stream.
+        tr: uint8 CUDA tensor [n_keys, 64] (the .tr of PublicKeys / PrivateKeys).  mu_flag: 0 hashed, 1 ctx longer than 255 bytes,
+        2 malformed offsets or key index out of range; a flagged op's mu row is zero."""
+        null = C.c_void_p(0)
+        tr = tr.contiguous().view(-1, 64)
+        mu = torch.empty((max(n_ops, 1), _mu_lib.MU_LEN), dtype=torch.uint8, device=self.device)
+        flag = torch.empty(max(n_ops, 1), dtype=torch.int32, device=self.device)
+        _mu_lib.check(_mu_lib.load().mldsa_mu_compute(
+            self.hp._h, mode, _ptr(tr), tr.shape[0], _ptr(key_idx) if key_idx is not None else null,
+            _ptr(msg_buf) if msg_buf is not None else null, _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
+            _ptr(ctx_off) if ctx_off is not None else null, _ptr(mu), _ptr(flag), n_ops, _stream(self.device)))
+        return mu[:n_ops], flag[:n_ops]
+
+    def mu_scratch(self, n_ops, sign=False):
+        """device scratch of one full pass of verify_mu_device (sign=True: sign_mu_device) over n_ops operations; a smaller one,
+        down to a pass of min(n_ops, 64) operations, makes the call run in several passes"""
+        lib = _mu_lib.load()
+        nb = (lib.mldsa_mu_sign_scratch_bytes if sign else lib.mldsa_mu_verify_scratch_bytes)(self.pset, n_ops)
+        return torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+
+    def verify_mu_device(self, pks, mu, sigs, ok, n_ops, key_idx=None, mu_flag=None, scratch=None):
+        """mldsa_verify_mu: ML-DSA.Verify_internal from mu [n_ops, 64]; ok[op] = 1 iff accepted.  Asynchronous on the current
+        stream.  scratch: a uint8 CUDA tensor from mu_scratch() (None: one is allocated for the call)."""
+        null = C.c_void_p(0)
+        if scratch is None:
+            scratch = self.mu_scratch(n_ops)
+        _mu_lib.check(_mu_lib.load().mldsa_verify_mu(
+            self.hp._h, self.pset, _ptr(pks.rho), _ptr(pks.t1_d2_hat_mont), len(pks), _ptr(key_idx) if key_idx is not None else null,
+            _ptr(mu), _ptr(mu_flag) if mu_flag is not None else null, _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(),
+            _stream(self.device)))
+        return ok
+
+    def sign_mu_device(self, sks, mu, rnd, sigs, n_ops, key_idx=None, mu_flag=None, status=None, scratch=None):
+        """mldsa_sign_mu: ML-DSA.Sign_internal from mu [n_ops, 64] and rnd [n_ops, 32]; blocks like sign_device, and the scratch is
+        all zero when it returns."""
+        null = C.c_void_p(0)
+        if scratch is None:
+            scratch = self.mu_scratch(n_ops, sign=True)
+        _mu_lib.check(_mu_lib.load().mldsa_sign_mu(
+            self.hp._h, self.pset, _ptr(sks.rho), _ptr(sks.cap_k), _ptr(sks.s_1_hat_mont), _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont),
+            len(sks), _ptr(key_idx) if key_idx is not None else null, _ptr(mu), _ptr(mu_flag) if mu_flag is not None else null,
+            _ptr(rnd), _ptr(sigs), _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(),
+            _stream(self.device)))
+        return sigs
+
+    def _mu_rows(self, mus, n_ops):
+        return self._key_bytes(mus, _mu_lib.MU_LEN, "mu") if n_ops else torch.zeros((1, _mu_lib.MU_LEN), dtype=torch.uint8, device=self.device)
+
+    def _mu_key_idx(self, key_idx, n_keys, n_ops):
+        if key_idx is None and n_keys != n_ops:
+            key_idx = np.arange(n_ops, dtype=np.uint32) % n_keys
+        key_idx = _check_key_idx(key_idx, n_keys, n_ops)
+        return None if key_idx is None else torch.as_tensor(key_idx.view(np.int32)).to(self.device)
+
+    def verify_mu(self, pks, mus, sigs, key_idx=None):
+        """ML-DSA.Verify with an externally computed mu (external_mu) per operation: returns a bool array.  mus: list of 64-byte
+        strings or a uint8 tensor [n_ops, 64]; sigs as for verify (a signature of the wrong length verifies as False)."""
+        n_ops = len(mus)
+        wrong_len = None
+        if not isinstance(sigs, torch.Tensor):
+            wrong_len = np.array([len(s) != self.SIG_LEN for s in sigs], dtype=bool)
+            flat = b"".join(bytes(s) if len(s) == self.SIG_LEN else bytes(self.SIG_LEN) for s in sigs)
+            sigs = torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(self.device)
+        ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
+        self.verify_mu_device(pks, self._mu_rows(mus, n_ops), sigs, ok, n_ops, self._mu_key_idx(key_idx, len(pks), n_ops))
+        torch.cuda.synchronize(self.device)
+        res = ok[:n_ops].cpu().numpy().astype(bool)
+        if wrong_len is not None:
+            res &= ~wrong_len
+        return res
+
+    def try_sign_mu_with_seed(self, sks, mus, rnd, key_idx=None):
+        """ML-DSA.Sign with an externally computed mu (external_mu) per operation and one 32-byte rnd each (zeros = deterministic):
+        the signature try_sign_with_seed gives on the message behind mu.  Returns a uint8 tensor [n_ops, SIG_LEN]."""
+        n_ops = len(mus)
+        rnd = self._key_bytes(rnd, 32, "rnd") if n_ops else torch.zeros((1, 32), dtype=torch.uint8, device=self.device)
+        sigs = torch.empty((max(n_ops, 1), self.SIG_LEN), dtype=torch.uint8, device=self.device)
+        status = torch.zeros(max(n_ops, 1), dtype=torch.int32, device=self.device)
+        self.sign_mu_device(sks, self._mu_rows(mus, n_ops), rnd, sigs, n_ops, self._mu_key_idx(key_idx, len(sks), n_ops), status=status)
+        if n_ops and int(status[:n_ops].min()) < 0:
+            bad = int(np.flatnonzero(status[:n_ops].cpu().numpy() < 0)[0])
+            raise ValueError(f"ML-DSA.Sign from mu: operation refused (op {bad})")
+        return sigs[:n_ops]
 
 
     # ---- incremental pre-hash and HashML-DSA from host memory (include/mldsa_ph.h) -------------

@@ -1,0 +1,455 @@
+"""External-mu ML-DSA on the device (include/mldsa_mu.h): mldsa_mu_compute against hashlib, mldsa_verify_mu against mldsa_verify and
+the oracle, mldsa_sign_mu against the oracle and mldsa_sign byte for byte, across passes, compactions, refusals and streams."""
+from gpu_common import *  # noqa: F401,F403
+from gpu_common import C, corruptions, dev, dev_off, fuzz_batch, hashlib, host, np, orc, pairs_ok, pytest, table, torch
+
+from conftest import PSET
+from fips204_amd import _lib, _mu_lib
+from fips204_amd.hotpath import _ptr, _stream
+from fips204_amd.ml_dsa import (MODE_INTERNAL, MODE_PREHASH, MODE_PURE, PH_SHA512, PublicKeys, _cat_with_offsets, external_mu,
+                                hash_message)
+
+pytestmark = pytest.mark.gpu
+
+SETS = (44, 65, 87)
+NULL = C.c_void_p(0)
+
+
+def le32(i):
+    return int(i).to_bytes(4, "little")
+
+
+def u8(rows, width):
+    return torch.frombuffer(bytearray(b"".join(rows) or bytes(width)), dtype=torch.uint8).cuda().view(-1, width)
+
+
+def kidx_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
+
+
+def scratch_for(m, n, sign=False):
+    """a scratch of exactly one pass over n ops, pre-filled so that stale bytes would show"""
+    lib = _mu_lib.load()
+    nb = (lib.mldsa_mu_sign_scratch_bytes if sign else lib.mldsa_mu_verify_scratch_bytes)(m.pset, n)
+    return torch.full((nb,), 0x5A, dtype=torch.uint8, device="cuda")
+
+
+def nonzero_bytes(m, t):
+    torch.cuda.synchronize()
+    nz = C.c_size_t()
+    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
+    return nz.value
+
+
+# ---------------------------------------------------------------------------------------------------------------- mu
+def raw_mu(m, mode, tr, kidx, msgs, moff, ctxs, coff, n, with_flag=True):
+    """mldsa_mu_compute into buffers with a canary row on either side: (mu [n, 64], flag [n]) as numpy"""
+    mu = torch.full((n + 2, 64), 0xA5, dtype=torch.uint8, device="cuda")
+    flag = torch.full((n + 2,), -7, dtype=torch.int32, device="cuda")
+    _mu_lib.check(_mu_lib.load().mldsa_mu_compute(
+        m.hp._h, mode, _ptr(tr), tr.shape[0], _ptr(kidx) if kidx is not None else NULL, _ptr(msgs) if msgs is not None else NULL, _ptr(moff),
+        _ptr(ctxs) if ctxs is not None else NULL, _ptr(coff) if coff is not None else NULL, _ptr(mu[1:]), _ptr(flag[1:]) if with_flag else NULL,
+        n, _stream(m.device)))
+    mu_h, flag_h = host(mu), host(flag)
+    assert (mu_h[0] == 0xA5).all() and (mu_h[-1] == 0xA5).all(), "canary behind mu"
+    assert flag_h[0] == -7 and flag_h[-1] == -7, "canary behind mu_flag"
+    if not with_flag:
+        assert (flag_h == -7).all()
+    return mu_h[1:-1], flag_h[1:-1]
+
+
+def m_prime(mode, ctx, msg):
+    return msg if mode == MODE_INTERNAL else bytes([1 if mode == MODE_PREHASH else 0, len(ctx)]) + ctx + msg
+
+
+TR = [hashlib.shake_256(b"mu-tr" + bytes([j])).digest(64) for j in range(3)]
+EDGES = (135, 136, 137, 271, 272, 273)  # 64 + |prefix| + |M| around one and two rate blocks
+
+
+def edge_batch(mode, n):
+    ctxs, msgs = [], []
+    for i in range(n):
+        ctx = b"" if mode == MODE_INTERNAL or i % 2 == 0 else hashlib.shake_128(b"mu-ctx" + le32(i)).digest(255)
+        pre = 0 if mode == MODE_INTERNAL else 2 + len(ctx)
+        if i % 7 == 6:
+            mlen = 0
+        else:
+            mlen = EDGES[i % 7] - 64 - pre
+            while mlen < 0:
+                mlen += 136
+        ctxs.append(ctx)
+        msgs.append(hashlib.shake_128(b"mu-edge" + le32(i)).digest(mlen))
+    return ctxs, msgs
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 200])
+@pytest.mark.parametrize("mode", [MODE_PURE, MODE_INTERNAL, MODE_PREHASH])
+def test_mu_compute_equals_hashlib(sets, mode, n):
+    m = sets[65]
+    ctxs, msgs = edge_batch(mode, n)
+    if n >= 64:  # every edge length occurs (with an empty ctx), and so does the empty message
+        assert set(EDGES) <= {64 + len(m_prime(mode, c, x)) for c, x in zip(ctxs, msgs)} and b"" in msgs
+        assert mode == MODE_INTERNAL or {len(c) for c in ctxs} == {0, 255}
+    mb, mo = _cat_with_offsets(msgs, m.device)
+    cb, co = _cat_with_offsets(ctxs, m.device)
+    kidx = np.arange(n, dtype=np.uint32) % 3
+    tr = u8(TR, 64)
+    want = [hashlib.shake_256(TR[kidx[i]] + m_prime(mode, ctxs[i], msgs[i])).digest(64) for i in range(n)]
+    got, flag = raw_mu(m, mode, tr, kidx_dev(kidx), mb, mo, cb, co, n)
+    assert (flag == 0).all()
+    assert [r.tobytes() for r in got] == want
+    # the helper and the Python wrapper agree with it; without ctx tables every ctx is empty; mu_flag may be NULL
+    assert want == [external_mu(TR[kidx[i]], msgs[i], ctxs[i], mode) for i in range(n)]
+    mu_t, flag_t = m.mu_device(tr, mb, mo, n, cb, co, kidx_dev(kidx), mode)
+    assert np.array_equal(host(mu_t), got) and not host(flag_t).any()
+    got0, _ = raw_mu(m, mode, tr, kidx_dev(kidx), mb, mo, None, None, n, with_flag=False)
+    assert [r.tobytes() for r in got0] == [hashlib.shake_256(TR[kidx[i]] + m_prime(mode, b"", msgs[i])).digest(64) for i in range(n)]
+
+
+def test_mu_compute_key_idx_null_long_ctx_and_bad_key(sets):
+    m = sets[44]
+    n = 70
+    tr_rows = [hashlib.shake_256(b"mu-tr-own" + le32(i)).digest(64) for i in range(n)]
+    msgs = [hashlib.shake_128(b"mu-own" + le32(i)).digest(3 * i) for i in range(n)]
+    ctxs = [bytes([i]) * (i % 5) for i in range(n)]
+    ctxs[9], ctxs[10], ctxs[66] = bytes(255), bytes(256), bytes(300)
+    mb, mo = _cat_with_offsets(msgs, m.device)
+    cb, co = _cat_with_offsets(ctxs, m.device)
+    got, flag = raw_mu(m, MODE_PURE, u8(tr_rows, 64), None, mb, mo, cb, co, n)  # key_idx NULL: op i uses key i
+    for i in range(n):
+        if len(ctxs[i]) > 255:
+            assert flag[i] == 1 and not got[i].any(), i
+        else:
+            assert flag[i] == 0 and got[i].tobytes() == external_mu(tr_rows[i], msgs[i], ctxs[i]), i
+    # ... with fewer keys than ops the ops past the table are refused (flag 2), and so is an index out of range
+    got, flag = raw_mu(m, MODE_PURE, u8(tr_rows[:40], 64), None, mb, mo, cb, co, n)
+    assert (flag[40:][[len(c) <= 255 for c in ctxs[40:]]] == 2).all() and flag[66] == 1 and not got[40:].any()
+    assert (flag[:40] == [1 if len(c) > 255 else 0 for c in ctxs[:40]]).all()
+    kidx = np.arange(n, dtype=np.uint32) % 40
+    kidx[5], kidx[64] = 40, 0xFFFFFFFF
+    got, flag = raw_mu(m, MODE_PURE, u8(tr_rows[:40], 64), kidx_dev(kidx), mb, mo, cb, co, n)
+    for i in range(n):
+        if i in (5, 64):
+            assert flag[i] == 2 and not got[i].any()
+        elif len(ctxs[i]) <= 255:
+            assert flag[i] == 0 and got[i].tobytes() == external_mu(tr_rows[kidx[i]], msgs[i], ctxs[i]), i
+    # in the internal mode the ctx tables are still checked and an over-long ctx still refuses the op, as in the core
+    got, flag = raw_mu(m, MODE_INTERNAL, u8(tr_rows, 64), None, mb, mo, cb, co, n)
+    assert flag[10] == 1 and flag[9] == 0 and got[9].tobytes() == external_mu(tr_rows[9], msgs[9], mode=MODE_INTERNAL)
+
+
+@pytest.mark.parametrize("which", ["msg", "ctx"])
+def test_mu_compute_refuses_malformed_offsets_unread(sets, which):
+    m = sets[65]
+    n = 200
+    rng = np.random.default_rng(77)
+    msgs = [hashlib.shake_128(b"mu-corr" + le32(i)).digest(1 + i % 40) for i in range(n)]
+    ctxs = [hashlib.shake_128(b"mu-corr-ctx" + le32(i)).digest(1 + i % 9) for i in range(n)]
+    mbuf, moff = table(msgs)
+    cbuf, coff = table(ctxs)
+    tr = u8(TR, 64)
+    kidx = np.arange(n, dtype=np.uint32) % 3
+    want = [external_mu(TR[kidx[i]], msgs[i], ctxs[i]) for i in range(n)]
+    damaged = corruptions(moff if which == "msg" else coff, rng)
+    for name, t in damaged.items():
+        okp = pairs_ok(t)
+        mo, co = (dev_off(t), dev_off(coff)) if which == "msg" else (dev_off(moff), dev_off(t))
+        got, flag = raw_mu(m, MODE_PURE, tr, kidx_dev(kidx), dev(mbuf), mo, dev(cbuf), co, n)
+        for i in range(n):
+            if not okp[i]:
+                assert flag[i] == 2 and not got[i].any(), (name, i)
+            else:
+                lo, hi = int(t[i]), int(t[i + 1])
+                if which == "msg":
+                    exp = external_mu(TR[kidx[i]], mbuf[lo:hi].tobytes(), ctxs[i])
+                elif hi - lo > 255:
+                    assert flag[i] == 1 and not got[i].any(), (name, i)
+                    continue
+                else:
+                    exp = external_mu(TR[kidx[i]], msgs[i], cbuf[lo:hi].tobytes())
+                assert flag[i] == 0 and got[i].tobytes() == exp, (name, i)
+        assert (flag != 0).tolist() == [not (okp[i]) or (which == "ctx" and int(t[i + 1]) - int(t[i]) > 255) for i in range(n)], name
+        if name == "equal_run":
+            assert okp.all() and got[0].tobytes() == want[0]
+    assert len(damaged) == 7
+
+
+# ------------------------------------------------------------------------------------------------------------ verify
+def expanded_pks(m, pk_all):
+    return m.public_keys_from_bytes(torch.from_numpy(np.ascontiguousarray(pk_all)).cuda())
+
+
+_FUZZ = {}
+
+
+def fuzz(m, pset):
+    """the shared verify batch of a set: 264 ops, 24 of each damage class, keys 4-7 random bytes; oracle verdicts computed once"""
+    if pset not in _FUZZ:
+        pk_all, kidx, msgs, sig, cls, changed = fuzz_batch(m, pset, 264, 4, 9000 + pset)
+        # fuzz_batch signs in pure mode with an empty ctx: M' = 0x00 | 0x00 | M is the message of the internal interface
+        msgs = [b"\x00\x00" + x for x in msgs]
+        pks = expanded_pks(m, pk_all)
+        tr = host(pks.tr)
+        opk = [orc.pk_try_from_bytes(pset, pk_all[j].tobytes()) for j in range(8)]
+        want = np.array([orc.verify_internal(pset, opk[kidx[i]], msgs[i], sig[i].tobytes()) for i in range(264)], dtype=bool)
+        mus = [external_mu(tr[kidx[i]].tobytes(), msgs[i], mode=MODE_INTERNAL) for i in range(264)]
+        _FUZZ[pset] = dict(pks=pks, kidx=kidx, msgs=msgs, sig=sig, want=want, mus=mus, changed=changed)
+    return _FUZZ[pset]
+
+
+def run_verify_mu(m, pks, mu, sig, n, kidx=None, flag=None, scratch=None):
+    ok = torch.full((n + 2,), 0xA5, dtype=torch.uint8, device="cuda")
+    m.verify_mu_device(pks, mu, sig, ok[1:], n, kidx, flag, scratch)
+    got = host(ok)
+    assert got[0] == 0xA5 and got[-1] == 0xA5
+    return got[1:-1].astype(bool)
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_verify_mu_on_the_fuzz_batch(sets, pset):
+    m = sets[pset]
+    f = fuzz(m, pset)
+    n, pks, want = 264, f["pks"], f["want"]
+    assert want.any() and not want.all() and want[~f["changed"]].all()
+    sig = dev(f["sig"])
+    kidx = kidx_dev(f["kidx"])
+    mb, mo = _cat_with_offsets(f["msgs"], m.device)
+    # mu from hashlib and mu from the device, against the core's own verify on the same device arrays and the oracle
+    mu_host = u8(f["mus"], 64)
+    mu_dev, flag = m.mu_device(pks.tr, mb, mo, n, key_idx=kidx, mode=MODE_INTERNAL)
+    assert torch.equal(mu_dev, mu_host) and not host(flag).any()
+    core = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    m.verify_device(pks, mb, mo, sig, core, n, key_idx=kidx, mode=MODE_INTERNAL)
+    got_host = run_verify_mu(m, pks, mu_host, sig, n, kidx)
+    got_dev = run_verify_mu(m, pks, mu_dev, sig, n, kidx, flag)
+    assert got_host.tolist() == want.tolist()
+    assert got_dev.tolist() == want.tolist()
+    assert host(core).astype(bool).tolist() == want.tolist()
+    # the list-level wrapper
+    assert m.verify_mu(pks, f["mus"], [s.tobytes() for s in f["sig"]], key_idx=f["kidx"]).tolist() == want.tolist()
+    # a scratch sized for 128 ops: three passes, identical verdicts
+    small = scratch_for(m, 128)
+    assert small.numel() < _mu_lib.load().mldsa_mu_verify_scratch_bytes(pset, 129)
+    assert run_verify_mu(m, pks, mu_host, sig, n, kidx, None, small).tolist() == want.tolist()
+    # below the minimum: refused, nothing written
+    tiny = small[:_mu_lib.load().mldsa_mu_verify_scratch_bytes(pset, 64) - 1]
+    with pytest.raises(_lib.MldsaError) as e:
+        m.verify_mu_device(pks, mu_host, sig, core, n, kidx, None, tiny)
+    assert e.value.code == _lib.ERR_NOMEM
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_verify_mu_one_key_per_op_and_small_batches(sets, pset):
+    m = sets[pset]
+    f = fuzz(m, pset)
+    pks, kidx, want = f["pks"], f["kidx"], f["want"]
+    sel = torch.from_numpy(kidx.astype(np.int64)).cuda()
+    own = PublicKeys(pset, pks.rho[sel].contiguous(), pks.tr[sel].contiguous(), pks.t1_d2_hat_mont[sel].contiguous())  # key i = the key of op i
+    sig, mu = dev(f["sig"]), u8(f["mus"], 64)
+    assert run_verify_mu(m, own, mu, sig, 264, None).tolist() == want.tolist()  # key_idx NULL
+    for n in (1, 63, 65):
+        assert run_verify_mu(m, own, mu, sig, n, None).tolist() == want[:n].tolist(), n
+        assert run_verify_mu(m, pks, mu, sig, n, kidx_dev(kidx[:n])).tolist() == want[:n].tolist(), n
+    # first ops of the batch are of class "good" (op 0) and damaged ones: both verdicts occur among the first 63
+    assert want[:63].any() and not want[:63].all()
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_verify_mu_refuses_flagged_ops_and_bad_key_indices(sets, pset):
+    m = sets[pset]
+    f = fuzz(m, pset)
+    n, want = 264, f["want"]
+    good = np.flatnonzero(want)
+    a, b, c = int(good[1]), int(good[len(good) // 2]), int(good[-1])
+    flag = np.zeros(n, dtype=np.int32)
+    flag[a], flag[b] = 1, 2
+    kidx = f["kidx"].copy()
+    kidx[c] = 8  # the table has 8 keys
+    got = run_verify_mu(m, f["pks"], u8(f["mus"], 64), dev(f["sig"]), n, kidx_dev(kidx), dev(flag))
+    exp = want.copy()
+    exp[[a, b, c]] = False
+    assert got.tolist() == exp.tolist()
+    kidx[c] = 0xFFFFFFFF
+    assert run_verify_mu(m, f["pks"], u8(f["mus"], 64), dev(f["sig"]), n, kidx_dev(kidx), dev(flag)).tolist() == exp.tolist()
+
+
+def test_verify_mu_acvp_sigver(sets, acvp_sigver):
+    """the sigVer vectors, fed the way tests/test_gpu_verify.py feeds them (expanded keys from the oracle), with mu from external_mu"""
+    n = 0
+    for g in acvp_sigver["testGroups"]:
+        m = sets[PSET[g["parameterSet"]]]
+        pk = orc.pk_try_from_bytes(m.pset, bytes.fromhex(g["pk"]))
+        k = m.params.k
+        d = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a[None], dtype=dt)).cuda()
+        tr = bytes(pk.tr)
+        pks = PublicKeys(m.pset, d(np.frombuffer(bytes(pk.rho), dtype=np.uint8), np.uint8), d(np.frombuffer(tr, dtype=np.uint8), np.uint8),
+                         d(np.ctypeslib.as_array(pk.t1_d2_hat_mont)[:k].copy(), np.int32))
+        mus = [external_mu(tr, bytes.fromhex(t["message"]), mode=MODE_INTERNAL) for t in g["tests"]]
+        sigs = [bytes.fromhex(t["signature"]) for t in g["tests"]]
+        got = m.verify_mu(pks, mus, sigs)
+        want = [t["testPassed"] for t in g["tests"]]
+        assert got.tolist() == want, [(t["tcId"], t["reason"]) for t, x, y in zip(g["tests"], got, want) if x != y]
+        n += len(want)
+    assert n == 45
+
+
+# -------------------------------------------------------------------------------------------------------------- sign
+_SIGN = {}
+
+
+def sign_batch(m, pset):
+    """the issue's signing batch of a set: 192 ops over 4 keys; oracle signatures and round counts computed once"""
+    if pset not in _SIGN:
+        n = 192
+        xi = [hashlib.sha256(b"mu-key" + bytes([pset]) + bytes([j])).digest() for j in range(4)]
+        pk, sk = m.keygen_from_seed(xi)
+        sks, pks = m.private_keys_from_bytes(sk), m.public_keys_from_bytes(pk)
+        skb = host(sk)
+        osk = [orc.sk_try_from_bytes(pset, skb[j].tobytes()) for j in range(4)]
+        kidx = np.arange(n, dtype=np.uint32) % 4
+        msgs = [hashlib.shake_128(b"mu-msg" + le32(i)).digest(7 * i % 300) for i in range(n)]
+        rnd = [bytes(32) if i % 2 == 0 else hashlib.sha256(b"mu-rnd" + le32(i)).digest() for i in range(n)]
+        want, iters = zip(*[orc.sign_internal(pset, osk[kidx[i]], msgs[i], rnd[i], mode=MODE_INTERNAL, want_iters=True) for i in range(n)])
+        tr = host(sks.tr)
+        mus = [external_mu(tr[kidx[i]].tobytes(), msgs[i], mode=MODE_INTERNAL) for i in range(n)]
+        _SIGN[pset] = dict(n=n, sks=sks, pks=pks, osk=osk, kidx=kidx, msgs=msgs, rnd=rnd, want=list(want), iters=list(iters), mus=mus)
+    return _SIGN[pset]
+
+
+def run_sign_mu(m, sks, mu, rnd, n, kidx=None, flag=None, scratch=None, check_scratch=True):
+    sigs = torch.full((n + 2, m.SIG_LEN), 0xA5, dtype=torch.uint8, device="cuda")
+    status = torch.full((n + 2,), -7, dtype=torch.int32, device="cuda")
+    if scratch is None:
+        scratch = scratch_for(m, n, sign=True)
+    m.sign_mu_device(sks, mu, rnd, sigs[1:], n, kidx, flag, status[1:], scratch)
+    if check_scratch:
+        assert nonzero_bytes(m, scratch) == 0, "the scratch is not all zero after mldsa_sign_mu"
+    sg, st = host(sigs), host(status)
+    assert (sg[0] == 0xA5).all() and (sg[-1] == 0xA5).all() and st[0] == -7 and st[-1] == -7
+    return [r.tobytes() for r in sg[1:-1]], st[1:-1]
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_sign_mu_equals_the_oracle_and_mldsa_sign(sets, pset):
+    m = sets[pset]
+    b = sign_batch(m, pset)
+    n, it = b["n"], b["iters"]
+    # the batch crosses many compactions and one op outlives the others: a change of inputs cannot quietly remove the tail
+    assert min(it) == 1 and max(it) >= 20, (min(it), max(it))
+    mu, rnd, kidx = u8(b["mus"], 64), u8(b["rnd"], 32), kidx_dev(b["kidx"])
+    got, st = run_sign_mu(m, b["sks"], mu, rnd, n, kidx)
+    assert not st.any()
+    assert got == b["want"], [i for i in range(n) if got[i] != b["want"][i]][:8]
+    mb, mo = _cat_with_offsets(b["msgs"], m.device)
+    core = torch.zeros((n, m.SIG_LEN), dtype=torch.uint8, device="cuda")
+    m.sign_device(b["sks"], mb, mo, rnd, core, n, key_idx=kidx, mode=MODE_INTERNAL)
+    assert [r.tobytes() for r in host(core)] == got
+    # verify_mu accepts all of them
+    assert run_verify_mu(m, b["pks"], mu, dev(np.frombuffer(b"".join(got), dtype=np.uint8)), n, kidx).all()
+    # a scratch sized for 128 ops: two passes, the same bytes, and all of it zero afterwards
+    small = scratch_for(m, 128, sign=True)
+    assert small.numel() < _mu_lib.load().mldsa_mu_sign_scratch_bytes(pset, 129)
+    got2, st2 = run_sign_mu(m, b["sks"], mu, rnd, n, kidx, None, small)
+    assert got2 == got and not st2.any()
+    # the list-level wrapper, on the first ops
+    sg = m.try_sign_mu_with_seed(b["sks"], b["mus"][:9], b["rnd"][:9], key_idx=b["kidx"][:9])
+    assert [r.tobytes() for r in host(sg)] == got[:9]
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_modes_end_to_end_external_mu_is_the_same_scheme(sets, pset):
+    m = sets[pset]
+    b = sign_batch(m, pset)
+    n = 16
+    sks, kidx_h = b["sks"], b["kidx"][:n]
+    kidx, rnd = kidx_dev(kidx_h), u8(b["rnd"][:n], 32)
+    msgs = b["msgs"][100:100 + n]
+    ctxs = [hashlib.shake_128(b"mu-e2e-ctx" + le32(i)).digest((17 * i) % 256) for i in range(n)]
+    cb, co = _cat_with_offsets(ctxs, m.device)
+    # ML-DSA.Sign: mu_compute(MODE_PURE, ctx) then sign_mu
+    mb, mo = _cat_with_offsets(msgs, m.device)
+    mu, flag = m.mu_device(sks.tr, mb, mo, n, cb, co, kidx, MODE_PURE)
+    got, st = run_sign_mu(m, sks, mu, rnd, n, kidx, flag)
+    want = [orc.sign_internal(pset, b["osk"][kidx_h[i]], msgs[i], b["rnd"][i], ctx=ctxs[i], mode=MODE_PURE) for i in range(n)]
+    assert not st.any() and got == want
+    assert run_verify_mu(m, b["pks"], mu, dev(np.frombuffer(b"".join(got), dtype=np.uint8)), n, kidx, flag).all()
+    # HashML-DSA.Sign: MODE_PREHASH on OID | SHA-512(M)
+    ph = [hash_message(x, PH_SHA512) for x in msgs]
+    pb, po = _cat_with_offsets(ph, m.device)
+    mu, flag = m.mu_device(sks.tr, pb, po, n, cb, co, kidx, MODE_PREHASH)
+    got, st = run_sign_mu(m, sks, mu, rnd, n, kidx, flag)
+    want = [orc.hash_sign(pset, b["osk"][kidx_h[i]], msgs[i], b["rnd"][i], ctxs[i], "SHA512") for i in range(n)]
+    assert not st.any() and got == want
+
+
+@pytest.mark.parametrize("pset", SETS)
+def test_sign_mu_refusals_leave_the_other_ops_alone(sets, pset):
+    m = sets[pset]
+    b = sign_batch(m, pset)
+    n = 70
+    mu, rnd = u8(b["mus"][:n], 64), u8(b["rnd"][:n], 32)
+    flag = np.zeros(n, dtype=np.int32)
+    flag[3], flag[40] = 1, 2
+    kidx = b["kidx"][:n].copy()
+    kidx[65] = 4  # four keys
+    got, st = run_sign_mu(m, b["sks"], mu, rnd, n, kidx_dev(kidx), dev(flag))
+    zero = bytes(m.SIG_LEN)
+    for i in range(n):
+        if i in (3, 40, 65):
+            assert got[i] == zero and st[i] == (_lib.ERR_CTX_LEN if i == 3 else _lib.ERR_PARAM), i
+        else:
+            assert got[i] == b["want"][i] and st[i] == 0, i
+    # status may be NULL
+    sigs = torch.full((n, m.SIG_LEN), 0xA5, dtype=torch.uint8, device="cuda")
+    m.sign_mu_device(b["sks"], mu, rnd, sigs, n, kidx_dev(kidx), dev(flag))
+    assert [r.tobytes() for r in host(sigs)] == got
+    # a call in which every op is refused returns, with zero signatures
+    got, st = run_sign_mu(m, b["sks"], mu[:5].contiguous(), rnd[:5].contiguous(), 5, kidx_dev(np.full(5, 9)), None)
+    assert got == [zero] * 5 and (st == _lib.ERR_PARAM).all()
+
+
+def test_sign_mu_reuse_of_a_scratch_and_two_streams(sets):
+    pset = 65
+    m = sets[pset]
+    b = sign_batch(m, pset)
+    n = 48
+    want_a, want_b = b["want"][:n], b["want"][n:2 * n]
+    mu_a, rnd_a, kidx_a = u8(b["mus"][:n], 64), u8(b["rnd"][:n], 32), kidx_dev(b["kidx"][:n])
+    mu_b, rnd_b, kidx_b = u8(b["mus"][n:2 * n], 64), u8(b["rnd"][n:2 * n], 32), kidx_dev(b["kidx"][n:2 * n])
+    # back to back on one scratch
+    scratch = scratch_for(m, n, sign=True)
+    got_a, _ = run_sign_mu(m, b["sks"], mu_a, rnd_a, n, kidx_a, None, scratch)
+    got_b, _ = run_sign_mu(m, b["sks"], mu_b, rnd_b, n, kidx_b, None, scratch)
+    assert got_a == want_a and got_b == want_b
+    # two streams, two scratches: the calls block their callers, so each gets a thread
+    torch.cuda.synchronize()
+    res, errs = {}, []
+    scr = {"a": scratch_for(m, n, sign=True), "b": scratch_for(m, n, sign=True)}
+    streams = {"a": torch.cuda.Stream(), "b": torch.cuda.Stream()}
+
+    def work(name, mu, rnd, kidx):
+        try:
+            with torch.cuda.stream(streams[name]):
+                sigs = torch.zeros((n, m.SIG_LEN), dtype=torch.uint8, device="cuda")
+                m.sign_mu_device(b["sks"], mu, rnd, sigs, n, kidx, None, None, scr[name])
+                streams[name].synchronize()
+                res[name] = [r.tobytes() for r in sigs.cpu().numpy()]
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+
+    ts = [threading.Thread(target=work, args=("a", mu_a, rnd_a, kidx_a)), threading.Thread(target=work, args=("b", mu_b, rnd_b, kidx_b))]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errs, errs
+    assert res["a"] == want_a and res["b"] == want_b
+    assert nonzero_bytes(m, scr["a"]) == 0 and nonzero_bytes(m, scr["b"]) == 0
+    # verify: two calls back to back on one scratch, asynchronous on one stream
+    vs = scratch_for(m, n)
+    sig_a, sig_b = dev(np.frombuffer(b"".join(want_a), dtype=np.uint8)), dev(np.frombuffer(b"".join(want_b), dtype=np.uint8))
+    ok_a = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    ok_b = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    m.verify_mu_device(b["pks"], mu_a, sig_a, ok_a, n, kidx_a, None, vs)
+    m.verify_mu_device(b["pks"], mu_a, sig_b, ok_b, n, kidx_b, None, vs)  # the other batch's signatures under this batch's mu
+    assert host(ok_a).all() and not host(ok_b).any()
