@@ -1,7 +1,7 @@
 """Builds fips204_amd/csrc/libmldsa_hip.so (hipcc, --offload-arch=gfx950) in-tree, then the layered libraries, which link the
 core and never rebuild it: the pre-hash library fips204_amd/ph/libmldsa_ph.so (include/mldsa_ph.h), the key-deduplication
-library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h) and the external-mu library fips204_amd/mu/libmldsa_mu.so
-(include/mldsa_mu.h)."""
+library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h), the external-mu library fips204_amd/mu/libmldsa_mu.so
+(include/mldsa_mu.h) and the seed-form key library fips204_amd/seed/libmldsa_seed.so (include/mldsa_seed.h)."""
 import os
 import subprocess
 
@@ -14,6 +14,8 @@ KEYS_DIR = os.path.join(_HERE, "keys")
 KEYS_LIB = os.path.join(KEYS_DIR, "libmldsa_keys.so")
 MU_DIR = os.path.join(_HERE, "mu")
 MU_LIB = os.path.join(MU_DIR, "libmldsa_mu.so")
+SEED_DIR = os.path.join(_HERE, "seed")
+SEED_LIB = os.path.join(SEED_DIR, "libmldsa_seed.so")
 
 
 def build(force=False, jobs=8):
@@ -23,7 +25,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB), (MU_DIR, MU_LIB)):
+    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB), (MU_DIR, MU_LIB), (SEED_DIR, SEED_LIB)):
         if force:
             subprocess.check_call(["make", "-C", layer_dir, "clean"], stdout=subprocess.DEVNULL)
         subprocess.check_call(["make", "-C", layer_dir, f"-j{jobs}"], stdout=subprocess.DEVNULL)

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keys_lib, _lib, _mu_lib, _ph_lib
+from . import _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
 from .hotpath import HotPath, N, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -92,6 +92,34 @@ def external_mu(tr, message, ctx=b"", mode=MODE_PURE):
     else:
         raise ValueError("mode: MODE_PURE, MODE_INTERNAL or MODE_PREHASH")
     return hashlib.shake_256(tr + m_prime).digest(64)
+
+
+FORM_SEED, FORM_EXPANDED, FORM_BOTH = "seed", "expanded", "both"
+
+
+def private_key_forms(seed=None, expanded=None):
+    """Names the encoding a private key arrived in and the route it takes to the device.  The certificate profile for ML-DSA gives a
+    private key three encodings: the 32-byte seed xi alone (preferred), the expanded wire key alone, or both -- and asks an importer
+    of "both" to check that the expanded key is the one the seed generates.  Returns (form, route):
+      (FORM_SEED, "expand_seeds")            MlDsa.expand_seeds_device
+      (FORM_EXPANDED, "sk_expand")           MlDsa.private_keys_from_bytes
+      (FORM_BOTH, "check_then_expand")       MlDsa.check_seeds_device, then expand_seeds_device for the keys that match
+    Pure Python: lengths only (the expanded key's length is the parameter set's, checked where it is used); no ASN.1."""
+    if seed is None and expanded is None:
+        raise ValueError("a private key needs a seed, an expanded key or both")
+    for name, key in (("seed", seed), ("expanded key", expanded)):
+        # bytes(32) would be 32 zero bytes: only bytes-like objects are keys
+        if key is not None and not isinstance(key, (bytes, bytearray, memoryview)):
+            raise TypeError(f"{name}: bytes, bytearray or memoryview expected, not {type(key).__name__}")
+    if seed is not None and memoryview(seed).nbytes != _seed_lib.SEED_LEN:
+        raise ValueError(f"seed: {_seed_lib.SEED_LEN} bytes expected")
+    if expanded is not None and memoryview(expanded).nbytes == 0:
+        raise ValueError("expanded key: empty")
+    if expanded is None:
+        return FORM_SEED, "expand_seeds"
+    if seed is None:
+        return FORM_EXPANDED, "sk_expand"
+    return FORM_BOTH, "check_then_expand"
 
 
 def _cat_with_offsets(items, device):
@@ -762,6 +790,77 @@ class MlDsa:
             raise ValueError(f"ML-DSA.Sign from mu: operation refused (op {bad})")
         return sigs[:n_ops]
 
+
+    # ---- private keys in seed form (include/mldsa_seed.h) -----------------------------------
+    def seed_scratch(self, n_keys, what="expand"):
+        """device scratch of one full pass of expand_seeds_device ("expand"), check_seeds_device ("check") or
+        sign_from_seeds_device ("sign") over n_keys seeds; a smaller one, down to a pass of min(n_keys, 64) keys, makes the call run
+        in several passes"""
+        lib = _seed_lib.load()
+        fn = {"expand": lib.mldsa_seed_expand_scratch_bytes, "check": lib.mldsa_seed_check_scratch_bytes,
+              "sign": lib.mldsa_seed_sign_scratch_bytes}[what]
+        return torch.empty(max(fn(self.pset, n_keys), 256), dtype=torch.uint8, device=self.device)
+
+    def expand_seeds_device(self, xi, out=None, want_pk=False, scratch=None):
+        """mldsa_seed_expand: ML-DSA.KeyGen_internal(xi) for a batch of 32-byte seeds, delivered as the PrivateKeys that the signing
+        calls take -- no wire-format private key is written.  want_pk: also return the wire public keys, uint8 [n, PK_LEN].
+        Asynchronous on the current stream; the scratch is all zero behind the call.  Returns PrivateKeys, or (PrivateKeys, pk)."""
+        xi = self._key_bytes(xi, _seed_lib.SEED_LEN, "xi")
+        n = xi.shape[0]
+        o = out if out is not None else self.empty_private_keys(n)
+        pk = torch.empty((n, self.PK_LEN), dtype=torch.uint8, device=self.device) if want_pk else None
+        if scratch is None:
+            scratch = self.seed_scratch(n)
+        _seed_lib.check(_seed_lib.load().mldsa_seed_expand(
+            self.hp._h, self.pset, _ptr(xi), _ptr(o.rho), _ptr(o.cap_k), _ptr(o.tr), _ptr(o.s_1_hat_mont), _ptr(o.s_2_hat_mont),
+            _ptr(o.t_0_hat_mont), _ptr(pk) if pk is not None else C.c_void_p(0), n, _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return (o, pk) if want_pk else o
+
+    def check_seeds_device(self, xi, sk_bytes, scratch=None):
+        """mldsa_seed_check: the consistency check of private keys that arrive as seed AND expanded key.  Returns a bool tensor:
+        True where sk_bytes[i] is byte for byte the private key ML-DSA.KeyGen_internal(xi[i]) generates."""
+        xi = self._key_bytes(xi, _seed_lib.SEED_LEN, "xi")
+        sk = self._key_bytes(sk_bytes, self.SK_LEN, "sk")
+        n = xi.shape[0]
+        if sk.shape[0] != n:
+            raise ValueError(f"{n} seeds but {sk.shape[0]} expanded keys")
+        match = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        if scratch is None:
+            scratch = self.seed_scratch(n, "check")
+        _seed_lib.check(_seed_lib.load().mldsa_seed_check(self.hp._h, self.pset, _ptr(xi), _ptr(sk), _ptr(match), n, _ptr(scratch),
+                                                          scratch.numel(), _stream(self.device)))
+        return match[:n].bool()
+
+    def sign_from_seeds_device(self, xi, msg_buf, msg_off, rnd, sigs, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE,
+                               status=None, scratch=None):
+        """mldsa_sign_seed: sign_device with the key table given as seeds xi (uint8 CUDA tensor [n_keys, 32]): the seeds are expanded
+        once per call into the scratch, which is all zero when the call returns.  Blocks like sign_device."""
+        null = C.c_void_p(0)
+        n_keys = xi.shape[0]
+        if scratch is None:
+            scratch = self.seed_scratch(n_keys, "sign")
+        _seed_lib.check(_seed_lib.load().mldsa_sign_seed(
+            self.hp._h, self.pset, mode, _ptr(xi), n_keys, _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
+            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
+            _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return sigs
+
+    def try_sign_from_seeds(self, xi, messages, rnd, ctxs=None, key_idx=None, mode=MODE_PURE):
+        """try_sign_with_seed with the private keys given as 32-byte seeds (list of bytes or uint8 tensor [n_keys, 32]): 32 bytes
+        uploaded per key instead of SK_LEN, and no expanded key outlives the call.  Returns a uint8 tensor [n_ops, SIG_LEN]."""
+        xi = self._key_bytes(xi, _seed_lib.SEED_LEN, "xi")
+        return self._sign_batch(xi, messages, rnd, ctxs, key_idx,
+                                lambda mb, mo, rn, sg, n, cb, co, ki, st: self.sign_from_seeds_device(xi, mb, mo, rn, sg, n, cb, co, ki, mode, st))
+
+    def private_keys_from_forms(self, seed=None, expanded=None):
+        """One private key in any of its three encodings (private_key_forms) -> PrivateKeys of length 1.  For "both" the expanded
+        key is checked against the seed first: ValueError when they disagree."""
+        form, _ = private_key_forms(seed, expanded)
+        if form == FORM_EXPANDED:
+            return self.private_keys_from_bytes([expanded])
+        if form == FORM_BOTH and not bool(self.check_seeds_device([seed], [expanded])[0]):
+            raise ValueError("private key: the expanded key is not the one the seed generates")
+        return self.expand_seeds_device([seed])
 
     # ---- incremental pre-hash and HashML-DSA from host memory (include/mldsa_ph.h) -------------
     def prehash_stream(self, n_ops, ph):
