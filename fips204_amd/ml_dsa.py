@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
 from .hotpath import HotPath, N, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -120,6 +120,35 @@ def private_key_forms(seed=None, expanded=None):
     if seed is None:
         return FORM_EXPANDED, "sk_expand"
     return FORM_BOTH, "check_then_expand"
+
+
+# parameter set -> (K, L, eta): what the layout of a wire private key depends on (FIPS 204 Table 1)
+_SK_SHAPE = {44: (4, 4, 2), 65: (6, 5, 4), 87: (8, 7, 2)}
+
+
+def private_key_faults(pset, sk_bytes):
+    """The range check skDecode (FIPS 204 Algorithm 25, lines 3 and 6) leaves to the importer, on the host: one uint8 per key with
+    _keycheck_lib.KEY_S1_RANGE (1) set where a field of the key's s1 section is above 2 eta -- a coefficient outside [-eta, eta] --
+    and KEY_S2_RANGE (2) likewise for s2; 0 = both vectors in range.  sk_bytes: one wire key (bytes-like), a list of them, or a uint8
+    array of n * SK_LEN bytes.  Pure numpy, no library and no device: what MlDsa.check_private_keys_device(level="range") reports."""
+    if pset not in _SK_SHAPE:
+        raise ValueError(f"unknown parameter set {pset!r}")
+    k, l, eta = _SK_SHAPE[pset]
+    bits = 3 if eta == 2 else 4
+    sk_len = 128 + 32 * bits * (l + k) + 416 * k
+    if isinstance(sk_bytes, (bytes, bytearray, memoryview)):
+        sk_bytes = [sk_bytes]
+    if isinstance(sk_bytes, np.ndarray):
+        a = np.ascontiguousarray(sk_bytes, dtype=np.uint8).reshape(-1)
+    else:
+        a = np.frombuffer(b"".join(bytes(b) for b in sk_bytes), dtype=np.uint8)
+    if a.size % sk_len:
+        raise ValueError(f"sk: {a.size} bytes are not a multiple of SK_LEN = {sk_len}")
+    a = a.reshape(-1, sk_len)
+    region = np.unpackbits(a[:, 128:128 + 32 * bits * (l + k)], axis=1, bitorder="little")
+    fields = region.reshape(a.shape[0], (l + k) * 256, bits).astype(np.uint8) @ (1 << np.arange(bits)).astype(np.uint8)
+    over = fields > 2 * eta
+    return (over[:, :l * 256].any(axis=1) * _keycheck_lib.KEY_S1_RANGE + over[:, l * 256:].any(axis=1) * _keycheck_lib.KEY_S2_RANGE).astype(np.uint8)
 
 
 def _cat_with_offsets(items, device):
@@ -861,6 +890,70 @@ class MlDsa:
         if form == FORM_BOTH and not bool(self.check_seeds_device([seed], [expanded])[0]):
             raise ValueError("private key: the expanded key is not the one the seed generates")
         return self.expand_seeds_device([seed])
+
+    # ---- strict import of wire private keys (include/mldsa_keycheck.h) ------------------------
+    def keycheck_scratch(self, n_keys):
+        """device scratch of one full pass of the pair check over n_keys keys; a smaller one, down to a pass of min(n_keys, 64) keys,
+        makes the call run in several passes"""
+        nb = _keycheck_lib.load().mldsa_keycheck_scratch_bytes(self.pset, n_keys)
+        return torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+
+    @staticmethod
+    def _keycheck_level(level):
+        if level not in _keycheck_lib.LEVELS:
+            raise ValueError('level: "range" or "pair"')
+        return _keycheck_lib.LEVELS[level]
+
+    def _sk_and_pk(self, sk_bytes, pk_bytes):
+        sk = self._key_bytes(sk_bytes, self.SK_LEN, "sk")
+        pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk") if pk_bytes is not None else None
+        if pk is not None and pk.shape[0] != sk.shape[0]:
+            raise ValueError(f"{sk.shape[0]} private keys but {pk.shape[0]} public keys")
+        return sk, pk
+
+    def check_private_keys_device(self, sk_bytes, pk_bytes=None, level="pair", scratch=None):
+        """mldsa_keypair_check (level="pair") or mldsa_sk_range_check (level="range") on wire private keys [n, SK_LEN]: a uint8 tensor
+        with one verdict per key, 0 = good, else the KEY_* bits of _keycheck_lib -- S1_RANGE 1, S2_RANGE 2 (a coefficient outside
+        [-eta, eta]), T0 4, TR 8 (the field does not belong to the key's rho, s1, s2), PK 16 (pk_bytes, wire public keys [n, PK_LEN],
+        given and not the key's).  A key with a range bit reports no other.  Asynchronous on the current stream; the scratch of the
+        pair check (keycheck_scratch(); None: allocated for the call) is all zero behind it."""
+        lvl = self._keycheck_level(level)
+        sk, pk = self._sk_and_pk(sk_bytes, pk_bytes)
+        n = sk.shape[0]
+        flag = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        lib = _keycheck_lib.load()
+        if lvl == _keycheck_lib.LEVEL_RANGE:
+            _keycheck_lib.check(lib.mldsa_sk_range_check(self.hp._h, self.pset, _ptr(sk), _ptr(flag), n, _stream(self.device)))
+        else:
+            if scratch is None:
+                scratch = self.keycheck_scratch(n)
+            _keycheck_lib.check(lib.mldsa_keypair_check(self.hp._h, self.pset, _ptr(sk), _ptr(pk) if pk is not None else C.c_void_p(0),
+                                                        _ptr(flag), n, _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return flag[:n]
+
+    def private_keys_try_from_bytes(self, sk_bytes, pk_bytes=None, level="pair", out=None, scratch=None):
+        """The strict counterpart of private_keys_from_bytes (mldsa_sk_import): the keys are expanded and checked at `level` as
+        check_private_keys_device checks them.  Raises ValueError naming the first flagged key and its bits (the fields of every
+        flagged key are zero by then); otherwise returns the PrivateKeys, byte for byte those of private_keys_from_bytes."""
+        lvl = self._keycheck_level(level)
+        sk, pk = self._sk_and_pk(sk_bytes, pk_bytes)
+        n = sk.shape[0]
+        o = out or self.empty_private_keys(n)
+        flag = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        null = C.c_void_p(0)
+        if lvl == _keycheck_lib.LEVEL_PAIR and scratch is None:
+            scratch = self.keycheck_scratch(n)
+        _keycheck_lib.check(_keycheck_lib.load().mldsa_sk_import(
+            self.hp._h, self.pset, lvl, _ptr(sk), _ptr(pk) if pk is not None else null, _ptr(o.rho), _ptr(o.cap_k), _ptr(o.tr),
+            _ptr(o.s_1_hat_mont), _ptr(o.s_2_hat_mont), _ptr(o.t_0_hat_mont), _ptr(flag), n, _ptr(scratch) if scratch is not None else null,
+            scratch.numel() if scratch is not None else 0, _stream(self.device)))
+        torch.cuda.synchronize(self.device)
+        verdict = flag[:n].cpu().numpy()
+        if verdict.any():
+            bad = int(np.flatnonzero(verdict)[0])
+            raise ValueError(f"private key {bad}: {_keycheck_lib.bit_names(int(verdict[bad]))} (flag {int(verdict[bad])}); "
+                             f"{int(np.count_nonzero(verdict))} of {n} keys refused")
+        return o
 
     # ---- incremental pre-hash and HashML-DSA from host memory (include/mldsa_ph.h) -------------
     def prehash_stream(self, n_ops, ph):

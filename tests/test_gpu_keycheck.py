@@ -1,0 +1,321 @@
+"""Strict import of wire private keys on the device (include/mldsa_keycheck.h): mldsa_sk_range_check, mldsa_keypair_check and
+mldsa_sk_import against the restatement of tests/keycheck_cases.py -- the ACVP keyGen pairs, every damage class between intact
+neighbours, with and without pk, across passes, refusals and streams, the zeroed scratch behind each call -- and the Python layer on
+top.  Every test runs for the three sets at n = 1 (one key), 64 (one full minimum pass) and 65 (the pass boundary)."""
+from gpu_common import *  # noqa: F401,F403
+from gpu_common import C, host, np, orc, pytest, shake, torch
+
+import keycheck_cases as kc
+from fips204_amd import _keycheck_lib, _lib
+from fips204_amd.hotpath import _ptr, _stream
+from fips204_amd.ml_dsa import MODE_PURE, private_key_faults
+
+pytestmark = pytest.mark.gpu
+
+SETS = kc.SETS
+SIZES = (1, 64, 65)
+NULL = C.c_void_p(0)
+CANARY_U8, CANARY_I32 = 0xA5, -7
+FIELDS = ("rho", "cap_k", "tr", "s_1_hat_mont", "s_2_hat_mont", "t_0_hat_mont")
+LEVELS = (("range", _keycheck_lib.LEVEL_RANGE), ("pair", _keycheck_lib.LEVEL_PAIR))
+sized = pytest.mark.parametrize("n", SIZES)
+per_set = pytest.mark.parametrize("pset", SETS)
+
+
+def lib():
+    return _keycheck_lib.load()
+
+
+def rows(keys):
+    """list of equally long byte strings -> uint8 device tensor [n, len]"""
+    return torch.frombuffer(bytearray(b"".join(keys)), dtype=torch.uint8).cuda().view(len(keys), -1)
+
+
+def scratch_bytes(m, n):
+    return lib().mldsa_keycheck_scratch_bytes(m.pset, n)
+
+
+def filled(nbytes):
+    """a scratch pre-filled so that stale bytes would show"""
+    return torch.full((max(nbytes, 256),), 0x5A, dtype=torch.uint8, device="cuda")
+
+
+def nonzero_bytes(m, t):
+    torch.cuda.synchronize()
+    nz = C.c_size_t()
+    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
+    return nz.value
+
+
+def flags_out(n):
+    return torch.full((n + 2,), CANARY_U8, dtype=torch.uint8, device="cuda")
+
+
+def read_flags(flag, written=True):
+    h = host(flag)
+    assert h[0] == CANARY_U8 and h[-1] == CANARY_U8, "canary beside flag"
+    if not written:
+        assert (h == CANARY_U8).all(), "flag was written"
+    return h[1:-1].tolist()
+
+
+def run_range(m, sks):
+    n = len(sks)
+    sk_d, flag = rows(sks), flags_out(n)
+    _keycheck_lib.check(lib().mldsa_sk_range_check(m.hp._h, m.pset, _ptr(sk_d), _ptr(flag[1:]), n, _stream(m.device)))
+    return read_flags(flag)
+
+
+def run_pair(m, sks, pks=None, scratch=None, sb=None, expect=_lib.OK):
+    """mldsa_keypair_check; checks that the whole scratch is zero afterwards"""
+    n = len(sks)
+    sk_d, pk_d, flag = rows(sks), (rows(pks) if pks is not None else None), flags_out(n)
+    if scratch is None:
+        scratch = filled(scratch_bytes(m, n))
+    rc = lib().mldsa_keypair_check(m.hp._h, m.pset, _ptr(sk_d), _ptr(pk_d) if pk_d is not None else NULL, _ptr(flag[1:]), n, _ptr(scratch),
+                                   scratch.numel() if sb is None else sb, _stream(m.device))
+    assert rc == expect, (rc, lib().mldsa_keycheck_last_error())
+    if rc != _lib.OK:
+        return read_flags(flag, written=False)
+    assert nonzero_bytes(m, scratch) == 0, "the scratch is not all zero after mldsa_keypair_check"
+    return read_flags(flag)
+
+
+def expected(pset, sks, pks=None):
+    return [kc.expected_flags(pset, sk, pks[i] if pks is not None else None) for i, sk in enumerate(sks)]
+
+
+_PAIRS = {}
+
+
+def pairs_of(pset):
+    if pset not in _PAIRS:
+        _PAIRS[pset] = kc.acvp_pairs(pset)
+    return _PAIRS[pset]
+
+
+def batch(pset, n, classes="abcdefg"):
+    """n key pairs; n = 64 and 65 deal the damage cases from different starting points, so that between them every case of every class
+    meets the device inside a batch (n = 1 tests take the cases one by one)"""
+    return kc.mixed_batch(pset, pairs_of(pset), n, classes, first=20 * (n % 2))
+
+
+def single_cases(pset, classes):
+    sk0, pk0 = pairs_of(pset)[0]
+    return [c for c in kc.damage_cases(pset, sk0, pk0) if c[0][0] in classes]
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1: ACVP
+@sized
+@per_set
+def test_every_acvp_keygen_pair_is_good(sets, pset, n):
+    m = sets[pset]
+    pairs = pairs_of(pset)
+    for first in range(0, len(pairs), n):  # n = 1: every pair on its own; n >= 64: all of them, cyclically, in one batch
+        chunk = [pairs[(first + i) % len(pairs)] for i in range(n)]
+        sks, pks = [p[0] for p in chunk], [p[1] for p in chunk]
+        assert run_pair(m, sks, pks) == [0] * n
+        assert run_pair(m, sks) == [0] * n
+        assert run_range(m, sks) == [0] * n
+    # two good keys with their public keys swapped: nothing but PK
+    if n >= 2:
+        pks[0], pks[1] = pks[1], pks[0]
+        assert run_pair(m, sks, pks) == [kc.PK, kc.PK] + [0] * (n - 2)
+
+
+# ----------------------------------------------------------------------------------------------------------------- 2: ranges
+@sized
+@per_set
+def test_range_check_equals_the_restatement(sets, pset, n):
+    m = sets[pset]
+    if n == 1:
+        for name, sk, _, _ in single_cases(pset, "ab"):
+            want = kc.expected_flags(pset, sk) & 3
+            assert (want != 0) == (name[0] == "a")
+            assert run_range(m, [sk]) == [want], name
+        return
+    sks, _, names = batch(pset, n, "ab")
+    want = [f & 3 for f in expected(pset, sks)]
+    assert {1, 2} <= set(want) and all(want[i] == 0 for i in range(0, n, 2))  # both bits occur; the neighbours of a damaged key are intact
+    assert want == private_key_faults(pset, sks).tolist()
+    got = run_range(m, sks)
+    assert got == want, [(i, names[i], got[i], want[i]) for i in range(n) if got[i] != want[i]][:8]
+
+
+# ------------------------------------------------------------------------------------------------------------ 3: the pair check
+@sized
+@per_set
+def test_keypair_check_equals_the_restatement(sets, pset, n):
+    m = sets[pset]
+    if n == 1:
+        for name, sk, pk, stated in single_cases(pset, "abcdefg"):
+            without, with_pk = kc.expected_flags(pset, sk), kc.expected_flags(pset, sk, pk)
+            assert stated is None or (without, with_pk) == stated
+            assert run_pair(m, [sk], [pk]) == [with_pk], name
+            assert run_pair(m, [sk]) == [without], name
+        return
+    sks, pks, names = batch(pset, n)
+    for use_pk in (True, False):
+        want = expected(pset, sks, pks if use_pk else None)
+        assert all(want[i] == 0 for i in range(0, n, 2)) and len(set(want)) >= 5
+        assert all(w in (0, 1, 2, 3) or not w & 3 for w in want)
+        got = run_pair(m, sks, pks if use_pk else None)
+        assert got == want, [(i, names[i], got[i], want[i]) for i in range(n) if got[i] != want[i]][:8]
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4: passes
+@sized
+@per_set
+def test_minimum_scratch_gives_the_same_flags_and_one_byte_less_is_refused(sets, pset, n):
+    m = sets[pset]
+    sks, pks, _ = batch(pset, n) if n > 1 else ([single_cases(pset, "f")[0][1]], [pairs_of(pset)[0][1]], None)
+    want = expected(pset, sks, pks)
+    one_pass, least = scratch_bytes(m, n), scratch_bytes(m, min(n, 64))
+    assert (least < one_pass) == (n > 64)  # n = 65: two passes, 64 + 1
+    scratch = filled(one_pass)
+    assert scratch.numel() == one_pass
+    assert run_pair(m, sks, pks, scratch=scratch) == want
+    assert run_pair(m, sks, pks, scratch=filled(least), sb=least) == want
+    # one byte below the minimum: refused before anything is launched, flag and scratch untouched
+    small = filled(least)
+    run_pair(m, sks, pks, scratch=small, sb=least - 1, expect=_lib.ERR_NOMEM)
+    assert b"scratch" in lib().mldsa_keycheck_last_error()
+    assert bool((small == 0x5A).all())
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5: import
+def run_import(m, level, sks, pks=None, scratch=None, sb=None, expect=_lib.OK):
+    """mldsa_sk_import into buffers with a canary row on either side; returns (flags, fields as numpy)"""
+    n, k, l = len(sks), m.params.k, m.params.l
+    shapes = dict(rho=(32,), cap_k=(32,), tr=(64,), s_1_hat_mont=(l, 256), s_2_hat_mont=(k, 256), t_0_hat_mont=(k, 256))
+    bufs = {}
+    for f, shp in shapes.items():
+        i32 = f.endswith("mont")
+        bufs[f] = torch.full((n + 2,) + shp, CANARY_I32 if i32 else CANARY_U8, dtype=torch.int32 if i32 else torch.uint8, device="cuda")
+    sk_d, pk_d, flag = rows(sks), (rows(pks) if pks is not None else None), flags_out(n)
+    pair = level == _keycheck_lib.LEVEL_PAIR
+    if scratch is None and pair:
+        scratch = filled(scratch_bytes(m, n))
+    rc = lib().mldsa_sk_import(
+        m.hp._h, m.pset, level, _ptr(sk_d), _ptr(pk_d) if pk_d is not None else NULL, *(_ptr(bufs[f][1:]) for f in FIELDS), _ptr(flag[1:]), n,
+        _ptr(scratch) if scratch is not None else NULL, 0 if scratch is None else (scratch.numel() if sb is None else sb), _stream(m.device))
+    assert rc == expect, (rc, lib().mldsa_keycheck_last_error())
+    if rc == _lib.OK and pair:
+        assert nonzero_bytes(m, scratch) == 0, "the scratch is not all zero after mldsa_sk_import"
+    out = {}
+    for f, t in bufs.items():
+        h = host(t)
+        can = CANARY_I32 if f.endswith("mont") else CANARY_U8
+        assert (h[0] == can).all() and (h[-1] == can).all(), f"canary beside {f}"
+        if rc != _lib.OK:
+            assert (h == can).all(), f"{f} was written"
+        out[f] = h[1:-1]
+    return read_flags(flag, written=rc == _lib.OK), out
+
+
+@sized
+@per_set
+def test_sk_import_is_sk_expand_for_good_keys_and_zero_for_flagged_ones(sets, pset, n):
+    m = sets[pset]
+    sks, pks, names = batch(pset, n) if n > 1 else ([pairs_of(pset)[0][0]], [pairs_of(pset)[0][1]], ["intact"])
+    plain = m.private_keys_from_bytes(rows(sks))
+    plain = {f: host(getattr(plain, f)).copy() for f in FIELDS}
+    for level_name, level in LEVELS:
+        pair = level == _keycheck_lib.LEVEL_PAIR
+        want = expected(pset, sks, pks) if pair else [f & 3 for f in expected(pset, sks)]
+        flags, got = run_import(m, level, sks, pks if pair else None)
+        assert flags == want, level_name
+        good = np.array(want) == 0
+        assert good.any() and (n == 1 or not good.all())
+        for f in FIELDS:
+            assert np.array_equal(got[f][good], plain[f][good]), (level_name, f, "a good key is not what mldsa_sk_expand gives")
+            assert not got[f][~good].any(), (level_name, f, "a row of a flagged key is not zero")
+            assert plain[f][~good].any() or n == 1
+    if n == 1:
+        # one flagged key on its own, at both levels; the range level lets a t0 fault through, as the plain import does
+        bad_range, bad_t0 = single_cases(pset, "a")[0][1], single_cases(pset, "c")[0][1]
+        for level_name, level in LEVELS:
+            flags, got = run_import(m, level, [bad_range])
+            assert flags == [kc.S1_RANGE] and not any(got[f].any() for f in FIELDS), level_name
+        flags, got = run_import(m, _keycheck_lib.LEVEL_PAIR, [bad_t0])
+        assert flags == [kc.T0] and not any(got[f].any() for f in FIELDS)
+        flags, got = run_import(m, _keycheck_lib.LEVEL_RANGE, [bad_t0])
+        assert flags == [0] and got["t_0_hat_mont"].any()
+    # the pair level with less than the minimum scratch: refused before anything is launched, nothing written
+    least = scratch_bytes(m, min(n, 64))
+    small = filled(least)
+    run_import(m, _keycheck_lib.LEVEL_PAIR, sks, pks, scratch=small, sb=least - 1, expect=_lib.ERR_NOMEM)
+    assert bool((small == 0x5A).all())
+    # ... and the minimum itself gives the same verdicts
+    flags, _ = run_import(m, _keycheck_lib.LEVEL_PAIR, sks, pks, scratch=filled(least), sb=least)
+    assert flags == expected(pset, sks, pks)
+
+
+@sized
+@per_set
+def test_a_key_imported_strictly_signs_what_the_oracle_signs(sets, pset, n):
+    m = sets[pset]
+    pairs = pairs_of(pset)
+    sks, pks = [pairs[i % len(pairs)][0] for i in range(n)], [pairs[i % len(pairs)][1] for i in range(n)]
+    keys = m.private_keys_try_from_bytes(sks, pks)
+    msgs = [shake(b"keycheck-msg", i, 20 + i) for i in range(n)]
+    rnd = [shake(b"keycheck-rnd", i) for i in range(n)]
+    sig = host(m.try_sign_with_seed(keys, msgs, rnd, mode=MODE_PURE))
+    for i in sorted({0, n // 2, n - 1}):
+        osk = orc.sk_try_from_bytes(pset, sks[i])
+        assert sig[i].tobytes() == orc.sign_internal(pset, osk, msgs[i], rnd[i], mode=MODE_PURE), i
+    assert m.verify_pk(rows(pks), msgs, torch.from_numpy(sig).cuda()).all()
+
+
+# ----------------------------------------------------------------------------------------------------------------- 6: streams
+@sized
+@per_set
+def test_a_non_default_stream_gives_the_same_flags(sets, pset, n):
+    m = sets[pset]
+    sks, pks, _ = batch(pset, n) if n > 1 else ([single_cases(pset, "g")[0][1]], [pairs_of(pset)[0][1]], None)
+    want = expected(pset, sks, pks)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert _stream(m.device).value == side.cuda_stream != torch.cuda.default_stream().cuda_stream
+        assert run_pair(m, sks, pks) == want
+        assert run_range(m, sks) == [w & 3 for w in expected(pset, sks)]
+        flags, _ = run_import(m, _keycheck_lib.LEVEL_PAIR, sks, pks)
+        assert flags == want
+
+
+# ------------------------------------------------------------------------------------------------------------- 7: Python layer
+@sized
+@per_set
+def test_python_layer_checks_and_imports(sets, pset, n):
+    m = sets[pset]
+    pairs = pairs_of(pset)
+    sks, pks = [pairs[i % len(pairs)][0] for i in range(n)], [pairs[i % len(pairs)][1] for i in range(n)]
+    for level in ("pair", "range"):
+        flag = m.check_private_keys_device(sks, pks if level == "pair" else None, level=level)
+        assert flag.dtype == torch.uint8 and flag.tolist() == [0] * n
+    keys = m.private_keys_try_from_bytes(rows(sks), rows(pks))
+    plain = m.private_keys_from_bytes(rows(sks))
+    assert len(keys) == n and all(torch.equal(getattr(keys, f), getattr(plain, f)) for f in FIELDS)
+    assert len(m.private_keys_try_from_bytes(sks, level="range")) == n
+    # the first flagged key is named with its bits
+    at = n // 2
+    bad = list(sks)
+    bad[at] = kc.flip(sks[at], kc.Layout(pset).t0 + 7, 0x20)
+    if n > 2:
+        bad[n - 1] = kc.flip(sks[n - 1], 70, 0x01)  # a later one does not change the message's key
+    assert m.check_private_keys_device(bad, pks).tolist() == expected(pset, bad, pks)
+    with pytest.raises(ValueError, match=rf"private key {at}: T0 \(flag 4\)"):
+        m.private_keys_try_from_bytes(bad, pks)
+    assert len(m.private_keys_try_from_bytes(bad, pks, level="range")) == n  # the range level does not look at t0
+    out_of_range = list(sks)
+    out_of_range[at] = kc.set_field(sks[at], kc.Layout(pset), "s2", 0, 5, 2 * kc.Layout(pset).eta + 1)
+    for level in ("pair", "range"):
+        with pytest.raises(ValueError, match=rf"private key {at}: S2_RANGE \(flag 2\)"):
+            m.private_keys_try_from_bytes(out_of_range, pks if level == "pair" else None, level=level)
+    with pytest.raises(ValueError, match="PK"):
+        m.private_keys_try_from_bytes(sks[:1], [kc.flip(pks[0], 100, 1)])
+    with pytest.raises(ValueError):
+        m.check_private_keys_device(sks, pks, level="strict")
+    with pytest.raises(ValueError):
+        m.check_private_keys_device(sks, pks[:-1] + [b"short"])
