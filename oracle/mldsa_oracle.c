@@ -868,10 +868,11 @@ static void compute_mu(const uint8_t tr[64], const uint8_t *msg, size_t mlen, co
 }
 
 /* ml_dsa.rs:153-337 sign_internal. Returns 0 on success, <0 on argument error
- * (lib.rs:274: ctx longer than 255 bytes). */
-int orc_sign_internal(int set, const orc_privkey *esk, const uint8_t *msg, size_t mlen,
-                      const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int mode,
-                      uint8_t *sig, int *iterations) {
+ * (lib.rs:274: ctx longer than 255 bytes).  `trace` (may be NULL): one record per attempt, the
+ * first `trace_cap` attempts; it only observes -- the loop and its decisions are the same. */
+static int sign_core(int set, const orc_privkey *esk, const uint8_t *msg, size_t mlen,
+                     const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int mode,
+                     uint8_t *sig, int *iterations, orc_sign_attempt *trace, size_t trace_cap) {
     const orc_params *p = orc_get_params(set);
     if (!p) return -1;
     if (ctxlen > 255) return -2;
@@ -919,6 +920,13 @@ int orc_sign_internal(int set, const orc_privkey *esk, const uint8_t *msg, size_
 
         int32_t z_norm = orc_infinity_norm(z, (size_t)l);   /* :277 */
         int32_t r0_norm = orc_infinity_norm(r0, (size_t)k); /* :278 */
+        orc_sign_attempt *rec = (trace && (size_t)(iters - 1) < trace_cap) ? &trace[iters - 1] : NULL;
+        if (rec) {
+            rec->z_norm = z_norm;
+            rec->r0_norm = r0_norm;
+            rec->ct0_norm = rec->d_norm = rec->hsum = -1;
+            rec->accept = 0;
+        }
         if (z_norm >= gamma1 - p->beta || r0_norm >= gamma2 - p->beta) { /* :280 */
             kappa = (uint16_t)(kappa + l);
             continue;
@@ -932,10 +940,18 @@ int orc_sign_internal(int set, const orc_privkey *esk, const uint8_t *msg, size_
             h[i] = orc_make_hint(gamma2, Q - ct0[i], orc_partial_reduce32(w[i] - cs2[i] + ct0[i]));
             hsum += h[i];
         }
-        if (orc_infinity_norm(ct0, (size_t)k) >= gamma2 || hsum > p->omega) { /* :312-319 */
+        int32_t ct0_norm = orc_infinity_norm(ct0, (size_t)k);
+        if (rec) {
+            for (int i = 0; i < k * N; i++) tmpK[i] = ct0[i] - cs2[i]; /* what a signer that transforms t0 - s2 once sees */
+            rec->ct0_norm = ct0_norm;
+            rec->d_norm = orc_infinity_norm(tmpK, (size_t)k);
+            rec->hsum = hsum;
+        }
+        if (ct0_norm >= gamma2 || hsum > p->omega) { /* :312-319 */
             kappa = (uint16_t)(kappa + l);
             continue;
         }
+        if (rec) rec->accept = 1;
         break;
     }
     for (int i = 0; i < l * N; i++) z[i] = orc_center_mod(z[i]); /* :334-335 */
@@ -943,6 +959,18 @@ int orc_sign_internal(int set, const orc_privkey *esk, const uint8_t *msg, size_
     free(a_hat);
     if (iterations) *iterations = iters;
     return 0;
+}
+
+int orc_sign_internal(int set, const orc_privkey *esk, const uint8_t *msg, size_t mlen,
+                      const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int mode,
+                      uint8_t *sig, int *iterations) {
+    return sign_core(set, esk, msg, mlen, ctx, ctxlen, rnd, mode, sig, iterations, NULL, 0);
+}
+
+int orc_sign_internal_trace(int set, const orc_privkey *esk, const uint8_t *msg, size_t mlen,
+                            const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int mode,
+                            uint8_t *sig, int *iterations, orc_sign_attempt *trace, size_t trace_cap) {
+    return sign_core(set, esk, msg, mlen, ctx, ctxlen, rnd, mode, sig, iterations, trace, trace_cap);
 }
 
 /* ml_dsa.rs:406-417 less ExpandA: w' = inv_ntt(A*ntt(z) - ntt(c) o t1_d2_hat_mont) */
@@ -1028,6 +1056,9 @@ typedef struct {
     size_t mlen, n_ops, repeat;
     const uint8_t *xi, *key_bytes;   /* kind 2: seeds; kinds 3 / 4: wire-format keys, deserialised per op */
     uint8_t *pk_out, *sk_out;
+    orc_sign_attempt *trace;         /* kind 5: sign with a trace of trace_cap records and an attempt count per op */
+    size_t trace_cap;
+    int32_t *iters_out;
 } mt_job;
 
 static void *mt_worker(void *arg) {
@@ -1056,6 +1087,13 @@ static void *mt_worker(void *arg) {
                 orc_sk_try_from_bytes(j->set, j->key_bytes + (size_t)k * (size_t)p->sk_len, &sk);
                 orc_sign_internal(j->set, &sk, j->msgs + i * j->mlen, j->mlen, NULL, 0, j->rnds + i * 32, j->mode,
                                   j->sigs_out + i * (size_t)p->sig_len, NULL);
+                continue;
+            }
+            if (j->kind == 5) {
+                int it = 0;
+                orc_sign_internal_trace(j->set, &j->sks[k], j->msgs + i * j->mlen, j->mlen, NULL, 0, j->rnds + i * 32, j->mode,
+                                        j->sigs_out + i * (size_t)p->sig_len, &it, j->trace + i * j->trace_cap, j->trace_cap);
+                j->iters_out[i] = it;
                 continue;
             }
             if (j->kind == 0)
@@ -1097,6 +1135,17 @@ void orc_sign_batch_mt(int set, const orc_privkey *sks, const uint32_t *key_idx,
     memset(&j, 0, sizeof(j));
     j.set = set; j.kind = 1; j.mode = mode; j.sks = sks; j.key_idx = key_idx; j.msgs = msgs; j.mlen = mlen;
     j.rnds = rnds; j.n_ops = n_ops; j.sigs_out = sigs; j.repeat = repeat;
+    mt_run(&j, n_threads);
+}
+
+void orc_sign_trace_batch_mt(int set, const orc_privkey *sks, const uint32_t *key_idx, const uint8_t *msgs, size_t mlen,
+                             const uint8_t *rnds, size_t n_ops, int mode, uint8_t *sigs, int32_t *iters,
+                             orc_sign_attempt *trace, size_t trace_cap, int n_threads) {
+    mt_job j;
+    memset(&j, 0, sizeof(j));
+    j.set = set; j.kind = 5; j.mode = mode; j.sks = sks; j.key_idx = key_idx; j.msgs = msgs; j.mlen = mlen;
+    j.rnds = rnds; j.n_ops = n_ops; j.sigs_out = sigs; j.repeat = 1;
+    j.iters_out = iters; j.trace = trace; j.trace_cap = trace_cap;
     mt_run(&j, n_threads);
 }
 

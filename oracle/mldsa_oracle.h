@@ -129,6 +129,18 @@ int  orc_sign_internal(int set, const orc_privkey *sk, const uint8_t *msg, size_
 int  orc_verify_internal(int set, const orc_pubkey *pk, const uint8_t *msg, size_t mlen,
                          const uint8_t *ctx, size_t ctxlen, const uint8_t *sig, int mode);
 
+/* orc_sign_internal with one record per attempt of the loop (ml_dsa.rs:212-330) written to trace[0 .. trace_cap):
+ * the norms the two tests compare (:277-280, :312), d_norm = ||c t0 - c s2||inf (centred) -- the quantity a signer
+ * that transforms t0 - s2 once per row has instead of c t0 --, the hint weight and whether the attempt was the
+ * accepted one.  An attempt that stops at :280 leaves ct0_norm, d_norm and hsum at -1.  *iterations counts every
+ * attempt, recorded or not.  Same signature bytes as orc_sign_internal. */
+typedef struct {
+    int32_t z_norm, r0_norm, ct0_norm, d_norm, hsum, accept;
+} orc_sign_attempt;
+int  orc_sign_internal_trace(int set, const orc_privkey *sk, const uint8_t *msg, size_t mlen,
+                             const uint8_t *ctx, size_t ctxlen, const uint8_t rnd[32], int mode,
+                             uint8_t *sig, int *iterations, orc_sign_attempt *trace, size_t trace_cap);
+
 /* verify-arithmetic unit of BASELINE config 2 (ml_dsa.rs:406-417 without ExpandA):
  * w' = inv_ntt(A_hat * ntt(z) - ntt(c) o t1_d2_hat_mont) */
 void orc_verify_arith(int k, int l, const int32_t *a_hat, const int32_t *z, const int32_t *c,
@@ -147,6 +159,11 @@ void orc_verify_batch_mt(int set, const orc_pubkey *pks, const uint32_t *key_idx
                          const uint8_t *sigs, size_t n_ops, int mode, uint8_t *ok, int n_threads, size_t repeat);
 void orc_sign_batch_mt(int set, const orc_privkey *sks, const uint32_t *key_idx, const uint8_t *msgs, size_t mlen,
                        const uint8_t *rnds, size_t n_ops, int mode, uint8_t *sigs, int n_threads, size_t repeat);
+
+/* orc_sign_internal_trace per op: iters[n_ops], trace[n_ops][trace_cap] */
+void orc_sign_trace_batch_mt(int set, const orc_privkey *sks, const uint32_t *key_idx, const uint8_t *msgs, size_t mlen,
+                             const uint8_t *rnds, size_t n_ops, int mode, uint8_t *sigs, int32_t *iters,
+                             orc_sign_attempt *trace, size_t trace_cap, int n_threads);
 
 /* keygen_from_seed + into_bytes per seed; try_from_bytes + verify / sign per op (the "from wire bytes" units) */
 void orc_keygen_batch_mt(int set, const uint8_t *xi, size_t n_keys, uint8_t *pk_out, uint8_t *sk_out, int n_threads, size_t repeat);

@@ -334,6 +334,26 @@ def sign_internal(pset, sk, msg, rnd, ctx=b"", mode=MODE_INTERNAL, want_iters=Fa
     return (bytes(sig), iters.value) if want_iters else bytes(sig)
 
 
+class SignAttempt(C.Structure):
+    """one attempt of the signing loop (orc_sign_attempt): ct0_norm / d_norm / hsum are -1 where the attempt stopped at ml_dsa.rs:280"""
+    _fields_ = [(n, C.c_int32) for n in ("z_norm", "r0_norm", "ct0_norm", "d_norm", "hsum", "accept")]
+
+
+TRACE_DTYPE = np.dtype([(n, np.int32) for n, _ in SignAttempt._fields_])
+
+
+def sign_internal_trace(pset, sk, msg, rnd, ctx=b"", mode=MODE_INTERNAL, cap=64):
+    """sign_internal + its per-attempt trace: (signature bytes, records [min(iterations, cap)] of TRACE_DTYPE, iterations)"""
+    sig = (C.c_uint8 * params(pset).sig_len)()
+    iters = C.c_int(0)
+    tr = np.zeros(cap, dtype=TRACE_DTYPE)
+    rc = lib().orc_sign_internal_trace(C.c_int(pset), C.byref(sk), _u8(msg), C.c_size_t(len(msg)), _u8(ctx), C.c_size_t(len(ctx)),
+                                       _u8(rnd), C.c_int(mode), sig, C.byref(iters), tr.ctypes.data_as(C.c_void_p), C.c_size_t(cap))
+    if rc != 0:
+        raise ValueError("ML-DSA.Sign: ctx too long" if rc == -2 else f"sign failed {rc}")
+    return bytes(sig), tr[:min(iters.value, cap)], iters.value
+
+
 def verify_internal(pset, pk, msg, sig, ctx=b"", mode=MODE_INTERNAL):
     if len(sig) != params(pset).sig_len:
         return False
@@ -367,6 +387,23 @@ def sign_batch_mt(pset, sks, key_idx, msgs, rnds, n_threads, repeat=1, mode=MODE
     sl = params(pset).sig_len
     raw = bytes(out)
     return [raw[i * sl:(i + 1) * sl] for i in range(n)]
+
+
+def sign_trace_batch_mt(pset, sks, key_idx, msgs, rnds, n_threads, mode=MODE_PURE, cap=64):
+    """sign_batch_mt through orc_sign_internal_trace: (signatures uint8 [n, SIG_LEN], iterations int32 [n], trace [n, cap] of
+    TRACE_DTYPE); op i's records are trace[i, :min(iterations[i], cap)], the rest of the row is zero."""
+    n = len(msgs)
+    arr = (PrivKey * len(sks))(*sks)
+    kidx = np.ascontiguousarray(key_idx, dtype=np.uint32)
+    mlen = len(msgs[0])
+    mb, rb = b"".join(msgs), b"".join(rnds)
+    sigs = np.zeros((n, params(pset).sig_len), dtype=np.uint8)
+    iters = np.zeros(n, dtype=np.int32)
+    trace = np.zeros((n, cap), dtype=TRACE_DTYPE)
+    lib().orc_sign_trace_batch_mt(C.c_int(pset), arr, kidx.ctypes.data_as(C.c_void_p), mb, C.c_size_t(mlen), rb, C.c_size_t(n),
+                                  C.c_int(mode), sigs.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p),
+                                  trace.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.c_int(n_threads))
+    return sigs, iters, trace
 
 
 def keygen_batch_mt(pset, xis, n_threads, repeat=1):

@@ -118,7 +118,8 @@ def test_multichunk_sign(sets, pset):
 def test_ml_dsa_44_ct0_bound_and_exact_test_agree(hp, sets):
     """ML-DSA-44: ||c t0||inf < gamma2 (ml_dsa.rs:312) CAN fail (tau * 2^12 > gamma2).  The hint stage's single transform per
     row gives ct0 - cs2, whose maximum + beta bounds ||ct0||inf; only if that bound cannot decide is ct0 transformed on its
-    own.  MLDSA_OPT_SIGN_CT0_EXACT = 1 takes the exact test for every surviving attempt: same signatures, same oracle."""
+    own.  MLDSA_OPT_SIGN_CT0_EXACT = 1 takes the exact test for every surviving attempt: same signatures, same oracle.
+    (Honest keys: both branches always say "ok" here.  tests/test_gpu_ct0_bound.py signs with keys whose t0 makes the test decide.)"""
     m = sets[44]
     n = 4096
     b = make_batch(m, n, 16, b"ct0")
