@@ -7,7 +7,7 @@ There is no fallback: a missing library is an ImportError with a build hint.
 import ctypes as C
 import os
 
-from . import _lib
+from . import _layer, _lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "mu", "libmldsa_mu.so")
@@ -35,27 +35,10 @@ _SIGNATURES = {
 }
 _RESTYPES = {"mldsa_mu_last_error": C.c_char_p, "mldsa_mu_verify_scratch_bytes": _SZ, "mldsa_mu_sign_scratch_bytes": _SZ}
 
-_lib_mu = None
-
 
 def load():
-    global _lib_mu
-    if _lib_mu is not None:
-        return _lib_mu
-    _lib.load()  # the core first: libmldsa_mu.so's NEEDED entry binds to it
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -m fips204_amd.build` "
-            "(make -C fips204_amd/mu after the core); there is no host fallback for signing or verifying from mu")
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
-    _lib_mu = lib
-    return lib
+    return _layer.load_layer(LIB_PATH, _SIGNATURES, _RESTYPES, "signing or verifying from mu")
 
 
 def check(rc):
-    if rc != _lib.OK:
-        raise _lib.MldsaError(rc, load().mldsa_mu_last_error().decode(errors="replace"))
+    _layer.check(rc, load().mldsa_mu_last_error)

@@ -7,7 +7,7 @@ mldsa_ctx).  There is no fallback: a missing library is an ImportError with a bu
 import ctypes as C
 import os
 
-from . import _lib
+from . import _layer, _lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "ph", "libmldsa_ph.so")
@@ -55,27 +55,10 @@ _SIGNATURES = {
 _RESTYPES = {"mldsa_ph_last_error": C.c_char_p, "mldsa_ph_scratch_bytes": _SZ, "mldsa_ph_state_bytes": _SZ,
              "mldsa_ph_host_destroy": None}
 
-_lib_ph = None
-
 
 def load():
-    global _lib_ph
-    if _lib_ph is not None:
-        return _lib_ph
-    _lib.load()  # the core first: libmldsa_ph.so's NEEDED entry binds to it
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -m fips204_amd.build` "
-            "(make -C fips204_amd/ph after the core); there is no host fallback for the device pre-hash")
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
-    _lib_ph = lib
-    return lib
+    return _layer.load_layer(LIB_PATH, _SIGNATURES, _RESTYPES, "the device pre-hash")
 
 
 def check(rc):
-    if rc != _lib.OK:
-        raise _lib.MldsaError(rc, load().mldsa_ph_last_error().decode(errors="replace"))
+    _layer.check(rc, load().mldsa_ph_last_error)

@@ -7,7 +7,7 @@ There is no fallback: a missing library is an ImportError with a build hint.
 import ctypes as C
 import os
 
-from . import _lib
+from . import _layer, _lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "seed", "libmldsa_seed.so")
@@ -37,27 +37,10 @@ _SIGNATURES = {
 _RESTYPES = {"mldsa_seed_last_error": C.c_char_p, "mldsa_seed_expand_scratch_bytes": _SZ, "mldsa_seed_check_scratch_bytes": _SZ,
              "mldsa_seed_sign_scratch_bytes": _SZ}
 
-_lib_seed = None
-
 
 def load():
-    global _lib_seed
-    if _lib_seed is not None:
-        return _lib_seed
-    _lib.load()  # the core first: libmldsa_seed.so's NEEDED entry binds to it
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -m fips204_amd.build` "
-            "(make -C fips204_amd/seed after the core); there is no host fallback for expanding or signing from seeds")
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
-    _lib_seed = lib
-    return lib
+    return _layer.load_layer(LIB_PATH, _SIGNATURES, _RESTYPES, "expanding or signing from seeds")
 
 
 def check(rc):
-    if rc != _lib.OK:
-        raise _lib.MldsaError(rc, load().mldsa_seed_last_error().decode(errors="replace"))
+    _layer.check(rc, load().mldsa_seed_last_error)

@@ -9,16 +9,13 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libmldsa_hip.so")
-PH_DIR = os.path.join(_HERE, "ph")
-PH_LIB = os.path.join(PH_DIR, "libmldsa_ph.so")
-KEYS_DIR = os.path.join(_HERE, "keys")
-KEYS_LIB = os.path.join(KEYS_DIR, "libmldsa_keys.so")
-MU_DIR = os.path.join(_HERE, "mu")
-MU_LIB = os.path.join(MU_DIR, "libmldsa_mu.so")
-SEED_DIR = os.path.join(_HERE, "seed")
-SEED_LIB = os.path.join(SEED_DIR, "libmldsa_seed.so")
-KEYCHECK_DIR = os.path.join(_HERE, "keycheck")
-KEYCHECK_LIB = os.path.join(KEYCHECK_DIR, "libmldsa_keycheck.so")
+# the layered libraries in build order: directory under fips204_amd/ -> library file name
+LAYERS = {"ph": "libmldsa_ph.so", "keys": "libmldsa_keys.so", "mu": "libmldsa_mu.so", "seed": "libmldsa_seed.so",
+          "keycheck": "libmldsa_keycheck.so"}
+# PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... KEYCHECK_LIB
+for _name, _file in LAYERS.items():
+    globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)
+    globals()[f"{_name.upper()}_LIB"] = os.path.join(_HERE, _name, _file)
 
 
 def build(force=False, jobs=8):
@@ -28,8 +25,9 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for layer_dir, layer_lib in ((PH_DIR, PH_LIB), (KEYS_DIR, KEYS_LIB), (MU_DIR, MU_LIB), (SEED_DIR, SEED_LIB),
-                                 (KEYCHECK_DIR, KEYCHECK_LIB)):
+    for name, file in LAYERS.items():
+        layer_dir = os.path.join(_HERE, name)
+        layer_lib = os.path.join(layer_dir, file)
         if force:
             subprocess.check_call(["make", "-C", layer_dir, "clean"], stdout=subprocess.DEVNULL)
         subprocess.check_call(["make", "-C", layer_dir, f"-j{jobs}"], stdout=subprocess.DEVNULL)

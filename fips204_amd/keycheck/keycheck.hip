@@ -7,11 +7,12 @@
 //                fields per lane): every field of a dword tested at once (field > 2 eta), ORed per vector and across the wave.
 //   k_kc_s1      one wave per polynomial of s1: four consecutive fields per lane -> eta - v as int32, the row mldsa_verify_arith reads.
 //   k_kc_row     one wave per row (key, i < K), four consecutive coefficients per lane: s2_i and the 13-bit t0_i fields from the wire
-//                key, t = A s1 + s2 mod q, Power2Round, r0 against the t0 field, t1 packed into the pk' row with the lane shuffles of
-//                k_seed_t (seed.hip) and compared with pk; row 0 also carries rho into pk' and compares it.
-//   k_kc_tr      tr' = H(pk', 64) as k_seed_tr computes it (one key per lane, rate blocks staged through an LDS tile; here the loads
-//                are unconditional and in flight twelve per lane at a time), compared with bytes 64 ... 127 of the key in registers: tr'
-//                is never stored.
+//                key, t = A s1 + s2 mod q, Power2Round, r0 against the t0 field, t1 packed into the pk' row with lane shuffles (a
+//                lane's 40 bits spread over the row's 80 dwords: whole, consecutive dword stores) and compared with pk; row 0 also
+//                carries rho into pk' and compares it.
+//   k_kc_tr      tr' = H(pk', 64): one key per lane, rate blocks staged through an LDS tile (the layout layer/layer_dev.h describes;
+//                here the loads are unconditional and in flight twelve per lane at a time), compared with bytes 64 ... 127 of the key
+//                in registers: tr' is never stored.
 //   k_kc_merge   the partial verdicts of a key -> its flag, the consistency bits masked where a range bit is set.
 //   k_kc_wipe    mldsa_sk_import: every output row of a flagged key -> zero (the flag is public by then).
 // s1, s2, t0 and every comparison against them are secret: no branch, trip count or address depends on them; the differences are
@@ -23,34 +24,19 @@
 #include <string>
 
 #include "../../include/mldsa_keycheck.h"
-#include "../csrc/field.h"
-#include "../csrc/keccak.h"
-#include "../csrc/rounding.h"
+#include "../layer/layer_dev.h"
+#include "../layer/layer_host.h"
 
 namespace {
 
-using mldsa::KeccakState;
-using mldsa::Q;
-using mldsa::SHAKE256_RATE;
+using namespace mldsa_layer;
 using mldsa::load_le32;
-using mldsa::u32_any;
-typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
 
-constexpr int RATE_DW = SHAKE256_RATE / 4;  // 34 dwords per rate block
-constexpr int TILE_STRIDE = RATE_DW + 1;    // odd row stride: the lanes' rows fall on different banks
 constexpr int STAGE_CHUNK = 12;             // loads of k_kc_tr in flight per lane: 34 = 12 + 12 + 10
-constexpr int T1_ROW_DW = 80;               // 256 coefficients of 10 bits
 constexpr int T0_ROW_BYTES = 416;           // 256 coefficients of 13 bits
 constexpr int SK_HEAD = 128;                // rho 32 | K 32 | tr 64
 constexpr int PART = 16;                    // partial verdict bytes per key: rows 0 ... K - 1, tr at 8, ranges at 9
 constexpr int PART_TR = 8, PART_RANGE = 9;
-
-// OR over the wave, the same word in every lane
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
 
 // --------------------------------------------------------------------------------------------------------------- ranges
 // 4-bit fields, v > 8: bit 3 set and any of bits 2 ... 0 (adding 7 to them carries into bit 3, never into the next field)
@@ -123,12 +109,6 @@ __global__ __launch_bounds__(256) void k_kc_s1(const uint8_t* __restrict__ sk, s
 }
 
 // ------------------------------------------------------------------------------------- t = A s1 + s2, Power2Round, t0, pk'
-// [0, q) + a small signed value -> [0, q)
-__device__ __forceinline__ int32_t canon(int32_t x) {
-    x += (x >> 31) & Q;
-    return x - (((Q - 1 - x) >> 31) & Q);
-}
-
 // w [n][K][256] canonical (mldsa_verify_arith's output); sk [n][sk_len]; pk [n][pk_len] or nullptr; pk_rows: pk', pk_len bytes apart
 // (rho | K rows of 320 bytes); part [n][PART].  Workgroup = 4 waves = 4 rows.
 __global__ __launch_bounds__(256) void k_kc_row(const int32_t* __restrict__ w, const uint8_t* __restrict__ sk, size_t sk_len,
@@ -277,37 +257,6 @@ __global__ __launch_bounds__(256) void k_kc_wipe(const uint8_t* __restrict__ fla
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-thread_local std::string g_err;
-
-int fail(int rc, const std::string& msg) {
-    g_err = msg;
-    return rc;
-}
-
-int core_failed(const char* fn, const char* core_fn, int rc) {
-    const char* m = mldsa_last_error();
-    return fail(rc, std::string(fn) + ": " + core_fn + ": " + (m ? m : "(no message)"));
-}
-
-int hip_failed(const char* fn, const char* what, hipError_t e) {
-    return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-}
-
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // Scratch layout of passes of up to n keys.  Every part is a multiple of 16 bytes per key, so every array starts 16-byte aligned.
 struct Layout {
     size_t a_hat, s1, w, zero, pk, part, bytes;
@@ -317,19 +266,14 @@ bool layout(int set, size_t n, Layout* o) {
     mldsa_params p;
     if (mldsa_get_params(set, &p) != MLDSA_OK || n > MLDSA_KEYCHECK_MAX_KEYS) return false;
     const size_t K = (size_t)p.k, L = (size_t)p.l;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += bytes;
-        return here;
-    };
-    o->a_hat = take(n * 1024 * K * L);
-    o->s1 = take(n * 1024 * L);
-    o->w = take(n * 1024 * K);
-    o->zero = take(n * 1024 * (K + 1));  // c [n][256], then t1 [n][K][256]
-    o->pk = take(n * (size_t)p.pk_len);
-    o->part = take(n * PART);
-    o->bytes = at;
+    Taker t;
+    o->a_hat = t.take(n * 1024 * K * L);
+    o->s1 = t.take(n * 1024 * L);
+    o->w = t.take(n * 1024 * K);
+    o->zero = t.take(n * 1024 * (K + 1));  // c [n][256], then t1 [n][K][256]
+    o->pk = t.take(n * (size_t)p.pk_len);
+    o->part = t.take(n * PART);
+    o->bytes = t.at;
     return true;
 }
 
@@ -337,31 +281,6 @@ size_t pass_bytes(int set, size_t n) {
     Layout Y;
     return layout(set, n, &Y) ? Y.bytes : 0;
 }
-
-// the largest pass P <= n whose scratch fits; 0 when not even the minimum does
-size_t pass_keys(int set, size_t n, size_t scratch_bytes) {
-    const size_t min_keys = n < 64 ? n : 64;
-    if (pass_bytes(set, min_keys) > scratch_bytes) return 0;
-    size_t lo = min_keys, hi = n;  // pass_bytes(lo) fits
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (pass_bytes(set, mid) <= scratch_bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-#define KC_CORE(call, name)                                      \
-    do {                                                         \
-        const int rc_ = (call);                                  \
-        if (rc_ != MLDSA_OK) return core_failed(fn, name, rc_);  \
-    } while (0)
-
-#define KC_LAUNCHED(what)                                       \
-    do {                                                        \
-        const hipError_t e_ = hipGetLastError();                \
-        if (e_ != hipSuccess) return hip_failed(fn, what, e_);  \
-    } while (0)
 
 int field_bits(const mldsa_params& p) { return p.eta == 2 ? 3 : 4; }
 
@@ -371,7 +290,7 @@ int launch_range(const char* fn, const mldsa_params& p, const uint8_t* sk, uint8
     const int s1_units = p.l * 8, n_units = (p.l + p.k) * 8;
     if (field_bits(p) == 3) hipLaunchKernelGGL(k_kc_range<3>, grid, block, 0, s, sk, (size_t)p.sk_len, s1_units, n_units, out, out_stride, n);
     else hipLaunchKernelGGL(k_kc_range<4>, grid, block, 0, s, sk, (size_t)p.sk_len, s1_units, n_units, out, out_stride, n);
-    KC_LAUNCHED("k_kc_range launch");
+    LAYER_LAUNCHED("k_kc_range launch");
     return MLDSA_OK;
 }
 
@@ -391,7 +310,7 @@ int pair_all(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, con
     uint8_t* part = base + Y.part;
     void* st = (void*)s;
     // nothing below writes the c and t1 rows: cleared once for every pass
-    KC_CORE(mldsa_memset(base + Y.zero, 0, pass * 1024 * (K + 1), st), "mldsa_memset");
+    LAYER_CORE(mldsa_memset(base + Y.zero, 0, pass * 1024 * (K + 1), st), "mldsa_memset");
     for (size_t key0 = 0; key0 < n_keys; key0 += pass) {
         const size_t n = n_keys - key0 < pass ? n_keys - key0 : pass;
         const uint8_t* sk0 = sk + key0 * skl;
@@ -401,35 +320,27 @@ int pair_all(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, con
         // rho [n][32] lies at the head of the rows A s1 is written to afterwards: mldsa_expand_a has read it by then (stream order)
         uint8_t* rho = reinterpret_cast<uint8_t*>(w);
         hipLaunchKernelGGL(k_kc_s1, dim3((unsigned)((n * L + 3) / 4)), dim3(256), 0, s, sk0, skl, s1, rho, p.l, bits, p.eta, n * L);
-        KC_LAUNCHED("k_kc_s1 launch");
-        KC_CORE(mldsa_expand_a(ctx, set, rho, a_hat, n, st), "mldsa_expand_a");
-        KC_CORE(mldsa_verify_arith(ctx, set, a_hat, s1, zero_c, zero_t1, w, n, st), "mldsa_verify_arith");
+        LAYER_LAUNCHED("k_kc_s1 launch");
+        LAYER_CORE(mldsa_expand_a(ctx, set, rho, a_hat, n, st), "mldsa_expand_a");
+        LAYER_CORE(mldsa_verify_arith(ctx, set, a_hat, s1, zero_c, zero_t1, w, n, st), "mldsa_verify_arith");
         hipLaunchKernelGGL(k_kc_row, dim3((unsigned)((n * K + 3) / 4)), dim3(256), 0, s, w, sk0, skl, pk0, pk_rows, pkl, part, p.k, p.l, bits,
                            p.eta, n * K);
-        KC_LAUNCHED("k_kc_row launch");
+        LAYER_LAUNCHED("k_kc_row launch");
         const dim3 grid((unsigned)((n + 63) / 64)), block(64);
         if (p.k == 4) hipLaunchKernelGGL(k_kc_tr<4>, grid, block, 0, s, pk_rows, sk0, skl, part, n);
         else if (p.k == 6) hipLaunchKernelGGL(k_kc_tr<6>, grid, block, 0, s, pk_rows, sk0, skl, part, n);
         else hipLaunchKernelGGL(k_kc_tr<8>, grid, block, 0, s, pk_rows, sk0, skl, part, n);
-        KC_LAUNCHED("k_kc_tr launch");
+        LAYER_LAUNCHED("k_kc_tr launch");
         hipLaunchKernelGGL(k_kc_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, flag + key0, p.k, n);
-        KC_LAUNCHED("k_kc_merge launch");
+        LAYER_LAUNCHED("k_kc_merge launch");
     }
-    return MLDSA_OK;
-}
-
-// the argument checks the three entry points share; *p is filled
-int check_common(const char* fn, mldsa_ctx* ctx, int set, size_t n_keys, mldsa_params* p) {
-    if (!ctx) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL context");
-    if (mldsa_get_params(set, p) != MLDSA_OK) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown parameter set");
-    if (n_keys > MLDSA_KEYCHECK_MAX_KEYS) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": more than MLDSA_KEYCHECK_MAX_KEYS keys");
     return MLDSA_OK;
 }
 
 // scratch of a pair check: MLDSA_ERR_PARAM / MLDSA_ERR_NOMEM, or the pass in *pass
 int check_scratch(const char* fn, int set, size_t n_keys, const void* scratch, size_t scratch_bytes, size_t* pass) {
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
-    *pass = pass_keys(set, n_keys, scratch_bytes);
+    *pass = largest_pass(n_keys, scratch_bytes, [set](size_t n) { return pass_bytes(set, n); });
     if (*pass == 0) return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below mldsa_keycheck_scratch_bytes(set, min(n_keys, 64))");
     return MLDSA_OK;
 }
@@ -442,7 +353,7 @@ struct ImportOut {
 // every output row of a flagged key -> zero
 int launch_wipe(const char* fn, const mldsa_params& p, const uint8_t* flag, const ImportOut& o, size_t n_keys, hipStream_t s) {
     hipLaunchKernelGGL(k_kc_wipe, dim3((unsigned)n_keys), dim3(256), 0, s, flag, o.rho, o.cap_k, o.tr, o.s1, o.s2, o.t0, p.k, p.l);
-    KC_LAUNCHED("k_kc_wipe launch");
+    LAYER_LAUNCHED("k_kc_wipe launch");
     return MLDSA_OK;
 }
 
@@ -453,9 +364,7 @@ int pair_checked(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p,
     int rc = pair_all(fn, ctx, set, p, sk, pk, flag, n_keys, pass, static_cast<uint8_t*>(scratch), s);
     if (rc == MLDSA_OK && wipe) rc = launch_wipe(fn, p, flag, *wipe, n_keys, s);
     // the scratch held s1 and A s1: cleared whatever happened above
-    const int zrc = mldsa_memset(scratch, 0, scratch_bytes, (void*)s);
-    if (rc != MLDSA_OK) return rc;
-    return zrc == MLDSA_OK ? MLDSA_OK : core_failed(fn, "mldsa_memset", zrc);
+    return cleared(fn, rc, scratch, scratch_bytes, s, false, "mldsa_memset");
 }
 
 }  // namespace
@@ -471,14 +380,11 @@ size_t mldsa_keycheck_scratch_bytes(int set, size_t n_keys) { return pass_bytes(
 int mldsa_sk_range_check(mldsa_ctx* ctx, int set, const uint8_t* sk, uint8_t* flag, size_t n_keys, void* stream) {
     const char* fn = "mldsa_sk_range_check";
     mldsa_params p;
-    const int arc = check_common(fn, ctx, set, n_keys, &p);
+    const int arc = check_common(fn, ctx, set, n_keys, MLDSA_KEYCHECK_MAX_KEYS, "MLDSA_KEYCHECK_MAX_KEYS keys", &p);
     if (arc != MLDSA_OK) return arc;
     if (n_keys == 0) return MLDSA_OK;
     if (!sk || !flag) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     return launch_range(fn, p, sk, flag, 1, n_keys, (hipStream_t)stream);
 }
 
@@ -486,17 +392,14 @@ int mldsa_keypair_check(mldsa_ctx* ctx, int set, const uint8_t* sk, const uint8_
                         size_t scratch_bytes, void* stream) {
     const char* fn = "mldsa_keypair_check";
     mldsa_params p;
-    const int arc = check_common(fn, ctx, set, n_keys, &p);
+    const int arc = check_common(fn, ctx, set, n_keys, MLDSA_KEYCHECK_MAX_KEYS, "MLDSA_KEYCHECK_MAX_KEYS keys", &p);
     if (arc != MLDSA_OK) return arc;
     if (n_keys == 0) return MLDSA_OK;
     if (!sk || !flag) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     size_t pass = 0;
     const int src = check_scratch(fn, set, n_keys, scratch, scratch_bytes, &pass);
     if (src != MLDSA_OK) return src;
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     return pair_checked(fn, ctx, set, p, sk, pk, flag, n_keys, pass, scratch, scratch_bytes, nullptr, (hipStream_t)stream);
 }
 
@@ -505,7 +408,7 @@ int mldsa_sk_import(mldsa_ctx* ctx, int set, int level, const uint8_t* sk, const
                     size_t scratch_bytes, void* stream) {
     const char* fn = "mldsa_sk_import";
     mldsa_params p;
-    const int arc = check_common(fn, ctx, set, n_keys, &p);
+    const int arc = check_common(fn, ctx, set, n_keys, MLDSA_KEYCHECK_MAX_KEYS, "MLDSA_KEYCHECK_MAX_KEYS keys", &p);
     if (arc != MLDSA_OK) return arc;
     if (level != MLDSA_KEYCHECK_RANGE && level != MLDSA_KEYCHECK_PAIR) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown level");
     if (n_keys == 0) return MLDSA_OK;
@@ -518,10 +421,7 @@ int mldsa_sk_import(mldsa_ctx* ctx, int set, int level, const uint8_t* sk, const
         const int src = check_scratch(fn, set, n_keys, scratch, scratch_bytes, &pass);
         if (src != MLDSA_OK) return src;
     }
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     const ImportOut out = {rho, cap_k, tr, s_1_hat_mont, s_2_hat_mont, t_0_hat_mont};
     const int xrc = mldsa_sk_expand(ctx, set, sk, rho, cap_k, tr, s_1_hat_mont, s_2_hat_mont, t_0_hat_mont, n_keys, stream);

@@ -23,8 +23,11 @@
 #include <string>
 
 #include "../../include/mldsa_keys.h"
+#include "../layer/layer_host.h"
 
 namespace {
+
+using namespace mldsa_layer;
 
 constexpr uint32_t NONE = 0xFFFFFFFFu;       // no slot / empty owner
 constexpr uint64_t EMPTY = ~(uint64_t)0;     // empty tag: what the clearing memset (0xFF) leaves
@@ -233,35 +236,6 @@ __global__ __launch_bounds__(256) void k_compose(const uint32_t* __restrict__ ke
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-thread_local std::string g_err;
-
-int fail(int rc, const std::string& msg) {
-    g_err = msg;
-    return rc;
-}
-
-int core_failed(const char* fn, const char* core_fn, int rc) {
-    const char* m = mldsa_last_error();
-    return fail(rc, std::string(fn) + ": " + core_fn + ": " + (m ? m : "(no message)"));
-}
-
-int hip_failed(const char* fn, const char* what, hipError_t e) {
-    return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-}
-
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 // scratch of the seam: [tags: 8 cap] [owners: 4 cap] [slot_of: 4 n_pad] [rep: 4 n_pad] [rank: 4 n_pad] [counts: 16 ceil(n_pad / 4096)]
@@ -324,12 +298,9 @@ int launch_dedup(const char* fn, int set, const uint8_t* pk, size_t n_keys, cons
     if (set == MLDSA_44) launch_gather<82>(pk, n, rep, rank, row_of, table, rows, s);
     else if (set == MLDSA_65) launch_gather<122>(pk, n, rep, rank, row_of, table, rows, s);
     else launch_gather<162>(pk, n, rep, rank, row_of, table, rows, s);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_failed(fn, "kernel launch", e);
+    LAYER_LAUNCHED("kernel launch");
     return MLDSA_OK;
 }
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // scratch of the op-level call, every part rounded up to 256 bytes
 struct VerifyLayout {
@@ -340,22 +311,18 @@ bool verify_layout(int set, size_t n, size_t m, VerifyLayout* o) {
     mldsa_params p;
     DedupLayout d;
     if (mldsa_get_params(set, &p) != MLDSA_OK || !dedup_layout(set, n, &d) || m > MLDSA_KEYS_MAX_CACHED) return false;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += round_up(bytes, 256);
-        return here;
-    };
-    o->dedup = take(d.bytes);
-    o->row_of = take(4 * n);
-    o->idx = take(4 * n);
-    o->n_rows = take(256);
-    o->table = take(m * (size_t)p.pk_len);
-    o->rho = take(32 * m);
-    o->tr = take(64 * m);
-    o->t1 = take(1024 * (size_t)p.k * m);
-    o->a_hat = take(1024 * (size_t)p.k * (size_t)p.l * m);
-    o->bytes = at;
+    Taker t;
+    t.round = 256;
+    o->dedup = t.take(d.bytes);
+    o->row_of = t.take(4 * n);
+    o->idx = t.take(4 * n);
+    o->n_rows = t.take(256);
+    o->table = t.take(m * (size_t)p.pk_len);
+    o->rho = t.take(32 * m);
+    o->tr = t.take(64 * m);
+    o->t1 = t.take(1024 * (size_t)p.k * m);
+    o->a_hat = t.take(1024 * (size_t)p.k * (size_t)p.l * m);
+    o->bytes = t.at;
     return true;
 }
 
@@ -392,10 +359,7 @@ int mldsa_keys_dedup(mldsa_ctx* ctx, int set, const uint8_t* pk, size_t n_keys, 
         if (!scratch || !aligned(scratch, 16) || scratch_bytes < L.bytes)
             return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL, misaligned or smaller than mldsa_keys_dedup_scratch_bytes");
     }
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     if (n_keys == 0) {
         const hipError_t e = hipMemsetAsync(n_rows, 0, 4, s);
@@ -428,10 +392,7 @@ int mldsa_verify_pk_dedup(mldsa_ctx* ctx, int set, int mode, const uint8_t* pk, 
     if (!aligned(pk, 16)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": pk must be 16-byte aligned");
     if (!scratch || !aligned(scratch, 256) || scratch_bytes < V.bytes)
         return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL, not 256-byte aligned or smaller than mldsa_keys_verify_scratch_bytes");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     uint8_t* base = static_cast<uint8_t*>(scratch);
     uint32_t* row_of = reinterpret_cast<uint32_t*>(base + V.row_of);
@@ -446,8 +407,7 @@ int mldsa_verify_pk_dedup(mldsa_ctx* ctx, int set, int mode, const uint8_t* pk, 
     if (key_idx) {
         hipLaunchKernelGGL(k_compose, dim3((unsigned)((n_ops + 255) / 256)), dim3(256), 0, s, key_idx, row_of, (uint32_t)n_keys, idx,
                            (uint32_t)n_ops);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_failed(fn, "k_compose launch", e);
+        LAYER_LAUNCHED("k_compose launch");
         use_idx = idx;
     }
     // the call's one host wait: the route depends on n_rows
@@ -468,10 +428,8 @@ int mldsa_verify_pk_dedup(mldsa_ctx* ctx, int set, int mode, const uint8_t* pk, 
     uint8_t* tr = base + V.tr;
     int32_t* t1 = reinterpret_cast<int32_t*>(base + V.t1);
     int32_t* a_hat = reinterpret_cast<int32_t*>(base + V.a_hat);
-    rc = mldsa_pk_expand(ctx, set, table, rho, tr, t1, rows, stream);
-    if (rc != MLDSA_OK) return core_failed(fn, "mldsa_pk_expand", rc);
-    rc = mldsa_expand_a(ctx, set, rho, a_hat, rows, stream);
-    if (rc != MLDSA_OK) return core_failed(fn, "mldsa_expand_a", rc);
+    LAYER_CORE(mldsa_pk_expand(ctx, set, table, rho, tr, t1, rows, stream), "mldsa_pk_expand");
+    LAYER_CORE(mldsa_expand_a(ctx, set, rho, a_hat, rows, stream), "mldsa_expand_a");
     rc = mldsa_verify_cached_a(ctx, set, mode, a_hat, tr, t1, rows, use_idx, msgs, msg_off, ctxs, ctx_off, sigs, ok, n_ops, stream);
     return rc == MLDSA_OK ? rc : core_failed(fn, "mldsa_verify_cached_a", rc);
 }

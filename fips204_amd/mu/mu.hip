@@ -7,7 +7,7 @@
 //   k_commit     the commitment hash of both directions: canonical w -> UseHint(h, w) (verify) or HighBits(w) (sign) -> w1Encode ->
 //                c_tilde = H(mu | w1, lambda / 4).  One sponge state per lane; for every rate block the wave packs the 64 ops' 34
 //                dwords cooperatively (consecutive lanes on consecutive dwords of one op: coalesced reads of w and h) into an LDS
-//                tile, then each lane absorbs its own row.  Verify compares with the signature's c_tilde and folds in the decode
+//                tile (the layout layer/layer_dev.h describes), then each lane absorbs its own row.  Verify compares with the signature's c_tilde and folds in the decode
 //                verdict, ||z||inf, mu_flag and the key flag; sign stores c_tilde.
 //   k_rhopp      rho'' = H(K[key] | rnd | mu, 64): one block per op, K gathered by the op's key index.
 //   k_accept     one signing round's accept step for one row per workgroup (one coefficient per thread): z = y + c s1,
@@ -26,21 +26,17 @@
 #include <string>
 
 #include "../../include/mldsa_mu.h"
-#include "../csrc/field.h"
-#include "../csrc/keccak.h"
-#include "../csrc/rounding.h"
+#include "../layer/layer_dev.h"
+#include "../layer/layer_host.h"
 
 namespace {
 
-using mldsa::KeccakState;
+using namespace mldsa_layer;
 using mldsa::Q;
 using mldsa::SHAKE256_RATE;
 using mldsa::load_le32;
-typedef uint32_t __attribute__((aligned(1))) u32_any;
 
-constexpr int RATE_DW = SHAKE256_RATE / 4;  // 34 dwords per rate block
-constexpr int TILE_STRIDE = RATE_DW + 1;    // odd row stride: the lanes' rows fall on different banks
-constexpr int SCAN_BLOCK = 256;             // rows per workgroup of the scan
+constexpr int SCAN_BLOCK = 256;  // rows per workgroup of the scan
 
 // -------------------------------------------------------------------------------------------------------------------- mu
 // The checks are k_mu's: the call vouches for [off[0], off[n_ops]); an op whose pair is not in order inside it is refused unread
@@ -336,11 +332,6 @@ __global__ __launch_bounds__(256) void k_gather_rows(const int32_t* __restrict__
 
 // canonical [0, q) -> (-q/2, q/2]
 __device__ __forceinline__ int32_t center_canon(int32_t x) { return x - ((((Q / 2) - x) >> 31) & Q); }
-// (-q, 2 q) -> [0, q)
-__device__ __forceinline__ int32_t canon(int32_t x) {
-    x += (x >> 31) & Q;
-    return x - (((Q - 1 - x) >> 31) & Q);
-}
 __device__ __forceinline__ int32_t iabs(int32_t x) { return x < 0 ? -x : x; }
 
 // Algorithm 7 lines 18-28 for row blockIdx.x, coefficient threadIdx.x of every polynomial.
@@ -456,47 +447,7 @@ __global__ __launch_bounds__(64) void k_zero_refused(uint8_t* __restrict__ sigs,
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-thread_local std::string g_err;
-
-int fail(int rc, const std::string& msg) {
-    g_err = msg;
-    return rc;
-}
-
-int core_failed(const char* fn, const char* core_fn, int rc) {
-    const char* m = mldsa_last_error();
-    return fail(rc, std::string(fn) + ": " + core_fn + ": " + (m ? m : "(no message)"));
-}
-
-int hip_failed(const char* fn, const char* what, hipError_t e) {
-    return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-}
-
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // Scratch layouts.  Every part is a multiple of 16 bytes per op, so every array starts 16-byte aligned in a 256-byte aligned scratch.
-struct Taker {
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t here = at;
-        at += bytes;
-        return here;
-    }
-};
-
 struct VerifyLayout {
     size_t a_hat, t1, h, w, z, c, rho, c_tilde, dec_ok, znorm, bytes;
 };
@@ -577,20 +528,6 @@ RowState row_state(uint8_t* base, const StateOff& s) {
     return r;
 }
 
-// the largest pass P <= n_ops whose scratch fits; 0 when not even the minimum does
-template <class Bytes>
-size_t pass_ops(size_t n_ops, size_t scratch_bytes, Bytes bytes) {
-    const size_t min_ops = n_ops < 64 ? n_ops : 64;
-    if (bytes(min_ops) > scratch_bytes) return 0;
-    size_t lo = min_ops, hi = n_ops;  // bytes(lo) fits
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (bytes(mid) <= scratch_bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 size_t verify_bytes(int set, size_t n) {
     VerifyLayout L;
     return verify_layout(set, n, &L) ? L.bytes : 0;
@@ -600,18 +537,6 @@ size_t sign_bytes(int set, size_t n) {
     SignLayout L;
     return sign_layout(set, n, &L) ? L.bytes : 0;
 }
-
-#define MU_CORE(call, name)                                  \
-    do {                                                     \
-        const int rc_ = (call);                              \
-        if (rc_ != MLDSA_OK) return core_failed(fn, name, rc_); \
-    } while (0)
-
-#define MU_LAUNCHED(what)                                       \
-    do {                                                        \
-        const hipError_t e_ = hipGetLastError();                \
-        if (e_ != hipSuccess) return hip_failed(fn, what, e_);  \
-    } while (0)
 
 template <bool VERIFY>
 void launch_commit(int set, const int32_t* w, const int32_t* h, const uint8_t* mu, size_t n, uint8_t* c_tilde, const CommitVerify& vd,
@@ -642,12 +567,12 @@ int verify_pass(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, 
     void* st = (void*)s;
 
     hipLaunchKernelGGL(k_gather_pk, dim3((unsigned)n), dim3(256), 0, s, rho, t1, (uint32_t)n_keys, key_idx, op0, p.k, rho_op, t1_op, key_bad);
-    MU_LAUNCHED("k_gather_pk launch");
-    MU_CORE(mldsa_sig_decode(ctx, set, pass_sigs, c_tilde, z, h, dec_ok, n, st), "mldsa_sig_decode");
-    MU_CORE(mldsa_sample_in_ball(ctx, set, c_tilde, c, n, st), "mldsa_sample_in_ball");
-    MU_CORE(mldsa_expand_a(ctx, set, rho_op, a_hat, n, st), "mldsa_expand_a");
-    MU_CORE(mldsa_verify_arith(ctx, set, a_hat, z, c, t1_op, w, n, st), "mldsa_verify_arith");
-    MU_CORE(mldsa_infinity_norm(ctx, z, (size_t)p.l, n, znorm, st), "mldsa_infinity_norm");
+    LAYER_LAUNCHED("k_gather_pk launch");
+    LAYER_CORE(mldsa_sig_decode(ctx, set, pass_sigs, c_tilde, z, h, dec_ok, n, st), "mldsa_sig_decode");
+    LAYER_CORE(mldsa_sample_in_ball(ctx, set, c_tilde, c, n, st), "mldsa_sample_in_ball");
+    LAYER_CORE(mldsa_expand_a(ctx, set, rho_op, a_hat, n, st), "mldsa_expand_a");
+    LAYER_CORE(mldsa_verify_arith(ctx, set, a_hat, z, c, t1_op, w, n, st), "mldsa_verify_arith");
+    LAYER_CORE(mldsa_infinity_norm(ctx, z, (size_t)p.l, n, znorm, st), "mldsa_infinity_norm");
     CommitVerify vd;
     vd.sigs = pass_sigs;
     vd.sig_len = (size_t)p.sig_len;
@@ -658,7 +583,7 @@ int verify_pass(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, 
     vd.key_bad = key_bad;
     vd.ok = ok + op0;
     launch_commit<true>(set, w, h, mu + op0 * MLDSA_MU_LEN, n, nullptr, vd, s);
-    MU_LAUNCHED("k_commit launch");
+    LAYER_LAUNCHED("k_commit launch");
     return MLDSA_OK;
 }
 
@@ -717,26 +642,26 @@ int sign_pass(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, co
     hipLaunchKernelGGL(k_rhopp, dim3((rows + 63) / 64), dim3(64), 0, s, k.cap_k, rnd + op0 * 32, rs[0], rows);
     hipLaunchKernelGGL(k_gather_rows, dim3(rows), dim3(256), 0, s, (const int32_t*)nullptr, (int32_t*)nullptr, (const uint32_t*)nullptr,
                        rs[0].key, k.s1, k.s2, k.t0, sec, p.k, p.l);
-    MU_LAUNCHED("prologue launch");
-    MU_CORE(mldsa_expand_a(ctx, set, rho_op, a_hat[0], n, st), "mldsa_expand_a");
+    LAYER_LAUNCHED("prologue launch");
+    LAYER_CORE(mldsa_expand_a(ctx, set, rho_op, a_hat[0], n, st), "mldsa_expand_a");
 
     const CommitVerify none = {};
     for (;;) {
         const uint32_t n_blocks = (rows + SCAN_BLOCK - 1) / SCAN_BLOCK;
-        MU_CORE(mldsa_expand_mask(ctx, set, rs[cur].rhopp, rs[cur].kappa, y, rows, st), "mldsa_expand_mask");
-        MU_CORE(mldsa_ntt(ctx, y, y_hat, rows * L, st), "mldsa_ntt");
-        MU_CORE(mldsa_mat_vec_mul(ctx, set, a_hat[cur], y_hat, w, rows, st), "mldsa_mat_vec_mul");
-        MU_CORE(mldsa_inv_ntt(ctx, w, w, rows * K, st), "mldsa_inv_ntt");
+        LAYER_CORE(mldsa_expand_mask(ctx, set, rs[cur].rhopp, rs[cur].kappa, y, rows, st), "mldsa_expand_mask");
+        LAYER_CORE(mldsa_ntt(ctx, y, y_hat, rows * L, st), "mldsa_ntt");
+        LAYER_CORE(mldsa_mat_vec_mul(ctx, set, a_hat[cur], y_hat, w, rows, st), "mldsa_mat_vec_mul");
+        LAYER_CORE(mldsa_inv_ntt(ctx, w, w, rows * K, st), "mldsa_inv_ntt");
         launch_commit<false>(set, w, nullptr, rs[cur].mu, rows, ct_row, none, s);
-        MU_LAUNCHED("k_commit launch");
-        MU_CORE(mldsa_sample_in_ball(ctx, set, ct_row, c, rows, st), "mldsa_sample_in_ball");
-        MU_CORE(mldsa_ntt(ctx, c, c, rows, st), "mldsa_ntt");
-        MU_CORE(mldsa_pointwise_mont(ctx, c, sec, cs, L + 2 * K, rows, st), "mldsa_pointwise_mont");
-        MU_CORE(mldsa_inv_ntt(ctx, cs, cs, rows * (L + 2 * K), st), "mldsa_inv_ntt");
+        LAYER_LAUNCHED("k_commit launch");
+        LAYER_CORE(mldsa_sample_in_ball(ctx, set, ct_row, c, rows, st), "mldsa_sample_in_ball");
+        LAYER_CORE(mldsa_ntt(ctx, c, c, rows, st), "mldsa_ntt");
+        LAYER_CORE(mldsa_pointwise_mont(ctx, c, sec, cs, L + 2 * K, rows, st), "mldsa_pointwise_mont");
+        LAYER_CORE(mldsa_inv_ntt(ctx, cs, cs, rows * (L + 2 * K), st), "mldsa_inv_ntt");
         launch_accept(set, y, w, cs, ct_row, rs[cur], p, z_out, h_out, ct_out, rows, s);
         hipLaunchKernelGGL(k_count, dim3(n_blocks), dim3(SCAN_BLOCK), 0, s, rs[cur].done, rows, counts);
         hipLaunchKernelGGL(k_offsets, dim3(1), dim3(64), 0, s, counts, n_blocks, d_live);
-        MU_LAUNCHED("round launch");
+        LAYER_LAUNCHED("round launch");
         uint32_t live = 0;  // the round's one look at the device
         e = hipMemcpyAsync(&live, d_live, 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -747,15 +672,15 @@ int sign_pass(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, co
             hipLaunchKernelGGL(k_compact, dim3(n_blocks), dim3(SCAN_BLOCK), 0, s, rs[cur], rows, counts, rs[nxt], src_of);
             hipLaunchKernelGGL(k_gather_rows, dim3(live), dim3(256), 0, s, a_hat[cur], a_hat[nxt], src_of, rs[nxt].key, k.s1, k.s2, k.t0, sec,
                                p.k, p.l);
-            MU_LAUNCHED("compaction launch");
+            LAYER_LAUNCHED("compaction launch");
             cur = nxt;
             rows = live;
         }
     }
     uint8_t* pass_sigs = sigs + op0 * (size_t)p.sig_len;
-    MU_CORE(mldsa_sig_encode(ctx, set, ct_out, z_out, h_out, pass_sigs, nullptr, n, st), "mldsa_sig_encode");
+    LAYER_CORE(mldsa_sig_encode(ctx, set, ct_out, z_out, h_out, pass_sigs, nullptr, n, st), "mldsa_sig_encode");
     hipLaunchKernelGGL(k_zero_refused, dim3((unsigned)n), dim3(64), 0, s, pass_sigs, (size_t)p.sig_len, bad);
-    MU_LAUNCHED("k_zero_refused launch");
+    LAYER_LAUNCHED("k_zero_refused launch");
     return MLDSA_OK;
 }
 
@@ -782,14 +707,11 @@ int mldsa_mu_compute(mldsa_ctx* ctx, int mode, const uint8_t* tr, size_t n_keys,
     if (!tr || !msg_off || !mu) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     if (n_keys == 0 || n_keys > 0xFFFFFFFFu) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": n_keys is 0 or does not fit 32 bits");
     if (n_ops > MLDSA_MU_MAX_OPS) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": more than MLDSA_MU_MAX_OPS ops");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mu_ext, dim3((unsigned)((n_ops + 63) / 64)), dim3(64), 0, s, tr, (uint32_t)n_keys, key_idx, mode, msgs, msg_off, ctxs,
                        ctx_off, mu, mu_flag, n_ops);
-    MU_LAUNCHED("k_mu_ext launch");
+    LAYER_LAUNCHED("k_mu_ext launch");
     return MLDSA_OK;
 }
 
@@ -806,12 +728,9 @@ int mldsa_verify_mu(mldsa_ctx* ctx, int set, const uint8_t* rho, const int32_t* 
     if (n_ops > MLDSA_MU_MAX_OPS) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": more than MLDSA_MU_MAX_OPS ops");
     if (!aligned(t1_d2_hat_mont, 16)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": t1_d2_hat_mont must be 16-byte aligned");
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
-    const size_t pass = pass_ops(n_ops, scratch_bytes, [set](size_t n) { return verify_bytes(set, n); });
+    const size_t pass = largest_pass(n_ops, scratch_bytes, [set](size_t n) { return verify_bytes(set, n); });
     if (pass == 0) return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below mldsa_mu_verify_scratch_bytes(set, min(n_ops, 64))");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     for (size_t op0 = 0; op0 < n_ops; op0 += pass) {
         const size_t n = n_ops - op0 < pass ? n_ops - op0 : pass;
         const int rc = verify_pass(fn, ctx, set, p, rho, t1_d2_hat_mont, n_keys, key_idx, mu, mu_flag, sigs, ok, op0, n,
@@ -836,12 +755,9 @@ int mldsa_sign_mu(mldsa_ctx* ctx, int set, const uint8_t* rho, const uint8_t* ca
     if (!aligned(s_1_hat_mont, 16) || !aligned(s_2_hat_mont, 16) || !aligned(t_0_hat_mont, 16))
         return fail(MLDSA_ERR_PARAM, std::string(fn) + ": the key polynomials must be 16-byte aligned");
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
-    const size_t pass = pass_ops(n_ops, scratch_bytes, [set](size_t n) { return sign_bytes(set, n); });
+    const size_t pass = largest_pass(n_ops, scratch_bytes, [set](size_t n) { return sign_bytes(set, n); });
     if (pass == 0) return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below mldsa_mu_sign_scratch_bytes(set, min(n_ops, 64))");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     const SignKeys keys = {rho, cap_k, s_1_hat_mont, s_2_hat_mont, t_0_hat_mont, n_keys, key_idx};
     int rc = MLDSA_OK;
@@ -849,7 +765,8 @@ int mldsa_sign_mu(mldsa_ctx* ctx, int set, const uint8_t* rho, const uint8_t* ca
         const size_t n = n_ops - op0 < pass ? n_ops - op0 : pass;
         rc = sign_pass(fn, ctx, set, p, keys, mu, mu_flag, rnd, sigs, status, op0, n, static_cast<uint8_t*>(scratch), s);
     }
-    // the scratch held rho'', y, c s1 ... and copies of K's users s1, s2, t0: cleared whatever happened above
+    // the scratch held rho'', y, c s1 ... and copies of K's users s1, s2, t0: cleared whatever happened above (written out, not the
+    // scaffold's cleared(): this call reports a failed clearing with the HIP runtime's message, not with the core's)
     hipError_t e = hipMemsetAsync(scratch, 0, scratch_bytes, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (rc != MLDSA_OK) return rc;

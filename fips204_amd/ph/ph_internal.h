@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/mldsa_ph.h"
+#include "../layer/layer_host.h"
 
 namespace mldsa_ph {
 
@@ -89,18 +90,9 @@ int fail(int rc, const std::string& msg);          // sets the thread's message,
 int core_failed(const char* fn, int rc);           // the same with the core's message
 int row_len_of(int ph);                            // negative for an unknown ph
 
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// the context's device for the call, the caller's current device afterwards: the layers' one (layer/layer_host.h).  Nothing else of that
+// scaffold is used here: the three objects of this library share one error slot, which prehash.hip defines
+using mldsa_layer::DeviceScope;
 
 // ---- incremental pre-hash (stream.hip) ----
 size_t state_bytes_of(int ph, size_t n_ops);       // 0 for an unknown ph or a size that does not fit

@@ -10,7 +10,7 @@
 //                as int32 for the NTT that follows, t1 packed into the key's pk row -- SimpleBitPack, 10 bits: a lane's 40 bits are
 //                spread over the row's 80 dwords with lane shuffles, so the stores are whole, consecutive dwords.
 //   k_seed_tr    tr = H(pk, 64): one key per lane on the lane-per-state Keccak, the 10 / 15 / 20 rate blocks staged cooperatively
-//                into an LDS tile (consecutive lanes on consecutive dwords of one key: coalesced loads), as k_commit of mu.hip does.
+//                into an LDS tile (the layout layer/layer_dev.h describes).
 //   k_seed_cmp   one wave per key: 16-byte loads of the generated and the presented wire key, differences ORed across the wave.
 //                The trip count depends on the parameter set only and every address on the key's number only: both keys are secret.
 #include <hip/hip_runtime.h>
@@ -20,22 +20,14 @@
 #include <string>
 
 #include "../../include/mldsa_seed.h"
-#include "../csrc/field.h"
-#include "../csrc/keccak.h"
-#include "../csrc/rounding.h"
+#include "../layer/layer_dev.h"
+#include "../layer/layer_host.h"
 
 namespace {
 
-using mldsa::KeccakState;
-using mldsa::Q;
+using namespace mldsa_layer;
 using mldsa::SHAKE256_RATE;
 using mldsa::load_le32;
-using mldsa::u32_any;
-typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
-
-constexpr int RATE_DW = SHAKE256_RATE / 4;  // 34 dwords per rate block
-constexpr int TILE_STRIDE = RATE_DW + 1;    // odd row stride: the lanes' rows fall on different banks
-constexpr int T1_ROW_DW = 80;               // 256 coefficients of 10 bits
 
 // ------------------------------------------------------------------------------------------------------------- seed hash
 // xi [n][32] -> rho [n][32], rho' [n][64], K [n][32]; rho also opens the key's wire public key (pk_rows, pk_len bytes apart)
@@ -83,12 +75,6 @@ __global__ __launch_bounds__(256) void k_seed_rows(const int32_t* __restrict__ s
 }
 
 // ------------------------------------------------------------------------------------------- t = A s1 + s2, Power2Round, pk
-// [0, q) + [-eta, eta] -> [0, q)
-__device__ __forceinline__ int32_t canon(int32_t x) {
-    x += (x >> 31) & Q;
-    return x - (((Q - 1 - x) >> 31) & Q);
-}
-
 // w [n][K][256] canonical (mldsa_inv_ntt's output); s1s2 [n][L + K][256]; t0 [n][K][256]; pk_rows: the keys' wire public keys,
 // pk_len bytes apart (rho | K rows of 320 bytes).  Workgroup = 4 waves = 4 rows.
 __global__ __launch_bounds__(256) void k_seed_t(const int32_t* __restrict__ w, const int32_t* __restrict__ s1s2, int32_t* __restrict__ t0,
@@ -184,42 +170,11 @@ __global__ __launch_bounds__(256) void k_seed_cmp(const uint8_t* __restrict__ a,
         diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
     }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) diff |= (uint32_t)__shfl_xor((int)diff, m, 64);
+    for (int m = 32; m >= 1; m >>= 1) diff |= (uint32_t)__shfl_xor((int)diff, m, 64);  // wave_or, written out
     if (lane == 0) match[key] = (uint8_t)(diff == 0);
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-thread_local std::string g_err;
-
-int fail(int rc, const std::string& msg) {
-    g_err = msg;
-    return rc;
-}
-
-int core_failed(const char* fn, const char* core_fn, int rc) {
-    const char* m = mldsa_last_error();
-    return fail(rc, std::string(fn) + ": " + core_fn + ": " + (m ? m : "(no message)"));
-}
-
-int hip_failed(const char* fn, const char* what, hipError_t e) {
-    return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-}
-
-// the context's device for the call, the caller's current device afterwards
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // Scratch layout of one expansion pass.  Every part is a multiple of 16 bytes per key, so every array starts 16-byte aligned.
 struct ExpandLayout {
     size_t a_hat, s1s2, w, rho_prime, pk, bytes;
@@ -229,18 +184,13 @@ bool expand_layout(int set, size_t n, ExpandLayout* o) {
     mldsa_params p;
     if (mldsa_get_params(set, &p) != MLDSA_OK || n > MLDSA_SEED_MAX_KEYS) return false;
     const size_t K = (size_t)p.k, L = (size_t)p.l;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += bytes;
-        return here;
-    };
-    o->a_hat = take(n * 1024 * K * L);
-    o->s1s2 = take(n * 1024 * (L + K));
-    o->w = take(n * 1024 * K);
-    o->rho_prime = take(n * 64);
-    o->pk = take(n * (size_t)p.pk_len);
-    o->bytes = at;
+    Taker t;
+    o->a_hat = t.take(n * 1024 * K * L);
+    o->s1s2 = t.take(n * 1024 * (L + K));
+    o->w = t.take(n * 1024 * K);
+    o->rho_prime = t.take(n * 64);
+    o->pk = t.take(n * (size_t)p.pk_len);
+    o->bytes = t.at;
     return true;
 }
 
@@ -256,32 +206,6 @@ size_t check_bytes(int set, size_t n) {
 }
 
 size_t table_bytes(const mldsa_params& p, size_t n) { return n * (1024 * (size_t)(p.l + 2 * p.k) + 128); }
-
-// the largest pass P <= n whose scratch fits; 0 when not even the minimum does
-template <class Bytes>
-size_t pass_keys(size_t n, size_t scratch_bytes, Bytes bytes) {
-    const size_t min_keys = n < 64 ? n : 64;
-    if (bytes(min_keys) > scratch_bytes) return 0;
-    size_t lo = min_keys, hi = n;  // bytes(lo) fits
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (bytes(mid) <= scratch_bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-#define SEED_CORE(call, name)                                    \
-    do {                                                         \
-        const int rc_ = (call);                                  \
-        if (rc_ != MLDSA_OK) return core_failed(fn, name, rc_);  \
-    } while (0)
-
-#define SEED_LAUNCHED(what)                                     \
-    do {                                                        \
-        const hipError_t e_ = hipGetLastError();                \
-        if (e_ != hipSuccess) return hip_failed(fn, what, e_);  \
-    } while (0)
 
 struct ExpandOut {
     uint8_t *rho, *cap_k, *tr;
@@ -308,27 +232,27 @@ int expand_pass(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, 
 
     hipLaunchKernelGGL(k_seed_h, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, xi + key0 * 32, (uint32_t)p.k | ((uint32_t)p.l << 8), rho,
                        rho_prime, out.cap_k + key0 * 32, pk_rows, pkl, n);
-    SEED_LAUNCHED("k_seed_h launch");
-    SEED_CORE(mldsa_expand_a(ctx, set, rho, a_hat, n, st), "mldsa_expand_a");
-    SEED_CORE(mldsa_expand_s(ctx, set, rho_prime, s1s2, n, st), "mldsa_expand_s");
+    LAYER_LAUNCHED("k_seed_h launch");
+    LAYER_CORE(mldsa_expand_a(ctx, set, rho, a_hat, n, st), "mldsa_expand_a");
+    LAYER_CORE(mldsa_expand_s(ctx, set, rho_prime, s1s2, n, st), "mldsa_expand_s");
     hipLaunchKernelGGL(k_seed_rows, dim3((unsigned)n), dim3(256), 0, s, s1s2, s1, s2, p.k, p.l);
-    SEED_LAUNCHED("k_seed_rows launch");
-    SEED_CORE(mldsa_ntt(ctx, s1, s1, n * L, st), "mldsa_ntt");
-    SEED_CORE(mldsa_ntt(ctx, s2, s2, n * K, st), "mldsa_ntt");
-    SEED_CORE(mldsa_mat_vec_mul(ctx, set, a_hat, s1, w, n, st), "mldsa_mat_vec_mul");
-    SEED_CORE(mldsa_inv_ntt(ctx, w, w, n * K, st), "mldsa_inv_ntt");
+    LAYER_LAUNCHED("k_seed_rows launch");
+    LAYER_CORE(mldsa_ntt(ctx, s1, s1, n * L, st), "mldsa_ntt");
+    LAYER_CORE(mldsa_ntt(ctx, s2, s2, n * K, st), "mldsa_ntt");
+    LAYER_CORE(mldsa_mat_vec_mul(ctx, set, a_hat, s1, w, n, st), "mldsa_mat_vec_mul");
+    LAYER_CORE(mldsa_inv_ntt(ctx, w, w, n * K, st), "mldsa_inv_ntt");
     hipLaunchKernelGGL(k_seed_t, dim3((unsigned)((n * K + 3) / 4)), dim3(256), 0, s, w, s1s2, t0, pk_rows, pkl, p.k, p.l, n * K);
-    SEED_LAUNCHED("k_seed_t launch");
-    SEED_CORE(mldsa_ntt(ctx, t0, t0, n * K, st), "mldsa_ntt");
-    SEED_CORE(mldsa_to_mont(ctx, s1, s1, n * L, st), "mldsa_to_mont");
-    SEED_CORE(mldsa_to_mont(ctx, s2, s2, n * K, st), "mldsa_to_mont");
-    SEED_CORE(mldsa_to_mont(ctx, t0, t0, n * K, st), "mldsa_to_mont");
+    LAYER_LAUNCHED("k_seed_t launch");
+    LAYER_CORE(mldsa_ntt(ctx, t0, t0, n * K, st), "mldsa_ntt");
+    LAYER_CORE(mldsa_to_mont(ctx, s1, s1, n * L, st), "mldsa_to_mont");
+    LAYER_CORE(mldsa_to_mont(ctx, s2, s2, n * K, st), "mldsa_to_mont");
+    LAYER_CORE(mldsa_to_mont(ctx, t0, t0, n * K, st), "mldsa_to_mont");
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
     uint8_t* tr = out.tr + key0 * 64;
     if (p.k == 4) hipLaunchKernelGGL(k_seed_tr<4>, grid, block, 0, s, pk_rows, tr, n);
     else if (p.k == 6) hipLaunchKernelGGL(k_seed_tr<6>, grid, block, 0, s, pk_rows, tr, n);
     else hipLaunchKernelGGL(k_seed_tr<8>, grid, block, 0, s, pk_rows, tr, n);
-    SEED_LAUNCHED("k_seed_tr launch");
+    LAYER_LAUNCHED("k_seed_tr launch");
     return MLDSA_OK;
 }
 
@@ -350,9 +274,9 @@ int check_all(const char* fn, mldsa_ctx* ctx, int set, const mldsa_params& p, co
         const size_t n = n_keys - key0 < pass ? n_keys - key0 : pass;
         uint8_t* sk_gen = base;            // [n][SK_LEN]: a multiple of 16 bytes per key
         uint8_t* pk_gen = base + n * skl;  // [n][PK_LEN]
-        SEED_CORE(mldsa_keygen(ctx, set, xi + key0 * 32, pk_gen, sk_gen, n, (void*)s), "mldsa_keygen");
+        LAYER_CORE(mldsa_keygen(ctx, set, xi + key0 * 32, pk_gen, sk_gen, n, (void*)s), "mldsa_keygen");
         hipLaunchKernelGGL(k_seed_cmp, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, sk_gen, sk + key0 * skl, match + key0, (int)(skl / 16), n);
-        SEED_LAUNCHED("k_seed_cmp launch");
+        LAYER_LAUNCHED("k_seed_cmp launch");
     }
     return MLDSA_OK;
 }
@@ -382,52 +306,40 @@ int mldsa_seed_expand(mldsa_ctx* ctx, int set, const uint8_t* xi, uint8_t* rho, 
                       void* stream) {
     const char* fn = "mldsa_seed_expand";
     mldsa_params p;
-    if (!ctx) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL context");
-    if (mldsa_get_params(set, &p) != MLDSA_OK) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown parameter set");
-    if (n_keys > MLDSA_SEED_MAX_KEYS) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": more than MLDSA_SEED_MAX_KEYS keys");
+    const int arc = check_common(fn, ctx, set, n_keys, MLDSA_SEED_MAX_KEYS, "MLDSA_SEED_MAX_KEYS keys", &p);
+    if (arc != MLDSA_OK) return arc;
     if (n_keys == 0) return MLDSA_OK;
     if (!xi || !rho || !cap_k || !tr || !s_1_hat_mont || !s_2_hat_mont || !t_0_hat_mont)
         return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     if (!aligned(s_1_hat_mont, 16) || !aligned(s_2_hat_mont, 16) || !aligned(t_0_hat_mont, 16))
         return fail(MLDSA_ERR_PARAM, std::string(fn) + ": the key polynomials must be 16-byte aligned");
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
-    const size_t pass = pass_keys(n_keys, scratch_bytes, [set](size_t n) { return expand_bytes(set, n); });
+    const size_t pass = largest_pass(n_keys, scratch_bytes, [set](size_t n) { return expand_bytes(set, n); });
     if (pass == 0) return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below mldsa_seed_expand_scratch_bytes(set, min(n_keys, 64))");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     const ExpandOut out = {rho, cap_k, tr, s_1_hat_mont, s_2_hat_mont, t_0_hat_mont, pk};
     const int rc = expand_all(fn, ctx, set, p, xi, out, n_keys, pass, static_cast<uint8_t*>(scratch), s);
     // the scratch held rho', s1, s2, A s1 and t: cleared whatever happened above
-    const int zrc = mldsa_memset(scratch, 0, scratch_bytes, (void*)s);
-    if (rc != MLDSA_OK) return rc;
-    return zrc == MLDSA_OK ? MLDSA_OK : core_failed(fn, "mldsa_memset", zrc);
+    return cleared(fn, rc, scratch, scratch_bytes, s, false, "mldsa_memset");
 }
 
 int mldsa_seed_check(mldsa_ctx* ctx, int set, const uint8_t* xi, const uint8_t* sk, uint8_t* match, size_t n_keys, void* scratch,
                      size_t scratch_bytes, void* stream) {
     const char* fn = "mldsa_seed_check";
     mldsa_params p;
-    if (!ctx) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL context");
-    if (mldsa_get_params(set, &p) != MLDSA_OK) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown parameter set");
-    if (n_keys > MLDSA_SEED_MAX_KEYS) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": more than MLDSA_SEED_MAX_KEYS keys");
+    const int arc = check_common(fn, ctx, set, n_keys, MLDSA_SEED_MAX_KEYS, "MLDSA_SEED_MAX_KEYS keys", &p);
+    if (arc != MLDSA_OK) return arc;
     if (n_keys == 0) return MLDSA_OK;
     if (!xi || !sk || !match) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
-    const size_t pass = pass_keys(n_keys, scratch_bytes, [set](size_t n) { return check_bytes(set, n); });
+    const size_t pass = largest_pass(n_keys, scratch_bytes, [set](size_t n) { return check_bytes(set, n); });
     if (pass == 0) return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below mldsa_seed_check_scratch_bytes(set, min(n_keys, 64))");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     const int rc = check_all(fn, ctx, set, p, xi, sk, match, n_keys, pass, static_cast<uint8_t*>(scratch), s);
     // the scratch held the seeds' wire private keys: cleared whatever happened above
-    const int zrc = mldsa_memset(scratch, 0, scratch_bytes, (void*)s);
-    if (rc != MLDSA_OK) return rc;
-    return zrc == MLDSA_OK ? MLDSA_OK : core_failed(fn, "mldsa_memset", zrc);
+    return cleared(fn, rc, scratch, scratch_bytes, s, false, "mldsa_memset");
 }
 
 int mldsa_sign_seed(mldsa_ctx* ctx, int set, int mode, const uint8_t* xi, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
@@ -435,6 +347,7 @@ int mldsa_sign_seed(mldsa_ctx* ctx, int set, int mode, const uint8_t* xi, size_t
                     size_t n_ops, void* scratch, size_t scratch_bytes, void* stream) {
     const char* fn = "mldsa_sign_seed";
     mldsa_params p;
+    // check_common's checks, written out: the mode is refused before the key count
     if (!ctx) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL context");
     if (mldsa_get_params(set, &p) != MLDSA_OK) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown parameter set");
     if (!mode_ok(mode)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": unknown mode");
@@ -445,13 +358,10 @@ int mldsa_sign_seed(mldsa_ctx* ctx, int set, int mode, const uint8_t* xi, size_t
     if (!xi || !msg_off || !rnd || !sigs) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     if (!scratch || !aligned(scratch, 256)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": scratch is NULL or not 256-byte aligned");
     const size_t table = table_bytes(p, n_keys);
-    const size_t pass = scratch_bytes < table ? 0 : pass_keys(n_keys, scratch_bytes - table, [set](size_t n) { return expand_bytes(set, n); });
+    const size_t pass = scratch_bytes < table ? 0 : largest_pass(n_keys, scratch_bytes - table, [set](size_t n) { return expand_bytes(set, n); });
     if (pass == 0)
         return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": scratch is below the key table plus mldsa_seed_expand_scratch_bytes(set, min(n_keys, 64))");
-    const int dev = mldsa_ctx_device(ctx);
-    if (dev < 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": bad context");
-    DeviceScope ds(dev);
-    if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
+    LAYER_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     // the table: the int32 rows first (every array 16-byte aligned), then rho, K, tr
     uint8_t* base = static_cast<uint8_t*>(scratch);
@@ -471,10 +381,7 @@ int mldsa_sign_seed(mldsa_ctx* ctx, int set, int mode, const uint8_t* xi, size_t
         if (rc != MLDSA_OK) rc = core_failed(fn, "mldsa_sign", rc);
     }
     // the scratch held the expanded keys and what their expansion left: cleared whatever happened above
-    int zrc = mldsa_memset(scratch, 0, scratch_bytes, (void*)s);
-    if (zrc == MLDSA_OK) zrc = mldsa_stream_sync((void*)s);
-    if (rc != MLDSA_OK) return rc;
-    return zrc == MLDSA_OK ? MLDSA_OK : core_failed(fn, "clearing the scratch", zrc);
+    return cleared(fn, rc, scratch, scratch_bytes, s, true, "clearing the scratch");
 }
 
 }  // extern "C"

@@ -79,6 +79,8 @@ def test_layered_on_the_one_core_library(mu):
         assert name not in undefined, name
     assert not defined & set(_lib.declared_symbols())
     mk = open(os.path.join(MU_DIR, "Makefile")).read()
+    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
+    mk += open(os.path.join(MU_DIR, "..", "layer", "layer.mk")).read()
     assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
     assert "-Rpass-analysis=kernel-resource-usage" in mk
     from fips204_amd import build
@@ -185,7 +187,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(mu):
         assert any(stem in nm for nm in kernels), stem
     assert sum("k_commit" in nm for nm in kernels) == 6 and sum("k_accept" in nm for nm in kernels) == 3  # per set, verify and sign
     checked = 0
-    for f in sorted(os.listdir(MU_DIR)) + ["../../include/mldsa_mu.h", "../_mu_lib.py"]:
+    for f in sorted(os.listdir(MU_DIR)) + ["../../include/mldsa_mu.h", "../_mu_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
         path = os.path.normpath(os.path.join(MU_DIR, f))
         if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
             continue
@@ -198,11 +200,13 @@ def test_kernels_do_not_spill_and_sources_are_clean(mu):
         # plain C++ only: every store is an ordinary vector store the compiler emits
         assert not re.search(r"\basm\b", t), f
         assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 4
+    assert checked >= 6
     # the core's device headers are included, never copied
     src = open(os.path.join(MU_DIR, "mu.hip")).read()
+    assert '#include "../layer/layer_dev.h"' in src  # through the layers' shared device header: both links of the chain
+    dev = open(os.path.join(MU_DIR, "..", "layer", "layer_dev.h")).read()
     for h in ("../csrc/keccak.h", "../csrc/field.h", "../csrc/rounding.h"):
-        assert f'#include "{h}"' in src
+        assert f'#include "{h}"' in dev
 
 
 def test_external_mu_is_shake256_of_tr_and_the_formatted_message():

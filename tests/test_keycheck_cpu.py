@@ -52,6 +52,7 @@ def test_a_clean_build_of_the_layer_produces_the_library_and_leaves_the_core_alo
     for f in ("Makefile", "keycheck.hip"):
         shutil.copy(os.path.join(KC_DIR, f), shadow / f)
     os.symlink(build.CSRC, tmp_path / "fips204_amd" / "csrc")
+    os.symlink(os.path.join(os.path.dirname(KC_DIR), "layer"), tmp_path / "fips204_amd" / "layer")
     os.symlink(os.path.join(ROOT, "include"), tmp_path / "include")
     assert not (shadow / "libmldsa_keycheck.so").exists()
     subprocess.run(["make", "-C", str(shadow)], check=True, capture_output=True)
@@ -60,6 +61,8 @@ def test_a_clean_build_of_the_layer_produces_the_library_and_leaves_the_core_alo
     subprocess.run(["make", "-C", str(shadow), "clean"], check=True, capture_output=True)
     assert not (shadow / "libmldsa_keycheck.so").exists() and not list(shadow.glob("*.res")) and not list(shadow.glob("*.o"))
     mk = open(os.path.join(KC_DIR, "Makefile")).read()
+    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
+    mk += open(os.path.join(KC_DIR, "..", "layer", "layer.mk")).read()
     assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
     assert "-Rpass-analysis=kernel-resource-usage" in mk
 
@@ -235,7 +238,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(keycheck):
     assert sum("k_kc_tr" in nm for nm in kernels) == 3     # one per parameter set (K = 4, 6, 8)
     assert sum("k_kc_range" in nm for nm in kernels) == 2  # 3-bit fields (ML-DSA-44 and 87) and 4-bit fields (ML-DSA-65)
     checked = 0
-    for f in sorted(os.listdir(KC_DIR)) + ["../../include/mldsa_keycheck.h", "../_keycheck_lib.py"]:
+    for f in sorted(os.listdir(KC_DIR)) + ["../../include/mldsa_keycheck.h", "../_keycheck_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
         path = os.path.normpath(os.path.join(KC_DIR, f))
         if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
             continue
@@ -248,11 +251,13 @@ def test_kernels_do_not_spill_and_sources_are_clean(keycheck):
         # plain C++ only: every store is an ordinary vector store the compiler emits
         assert not re.search(r"\basm\b", t), f
         assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 4
+    assert checked >= 6
     # the core's device headers are included, never copied
     src = open(os.path.join(KC_DIR, "keycheck.hip")).read()
+    assert '#include "../layer/layer_dev.h"' in src  # through the layers' shared device header: both links of the chain
+    dev = open(os.path.join(KC_DIR, "..", "layer", "layer_dev.h")).read()
     for h in ("../csrc/keccak.h", "../csrc/field.h", "../csrc/rounding.h"):
-        assert f'#include "{h}"' in src
+        assert f'#include "{h}"' in dev
     # the range kernel has one loop, whose bound is the parameter set's, and leaves it by no other way; neither it nor the row kernel
     # asks the wave what its lanes found before the verdict byte
     rng_src = src[src.index("void k_kc_range"):src.index("// ---", src.index("void k_kc_range"))]

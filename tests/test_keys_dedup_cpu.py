@@ -74,6 +74,8 @@ def test_layered_on_the_one_core_library(keys):
     assert not defined & set(_lib.declared_symbols())
     # the Makefile links the core and never builds it
     mk = open(os.path.join(KEYS_DIR, "Makefile")).read()
+    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
+    mk += open(os.path.join(KEYS_DIR, "..", "layer", "layer.mk")).read()
     assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
     assert "-Rpass-analysis=kernel-resource-usage" in mk
 
@@ -198,7 +200,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(keys):
                               "dca" + "che_wb", "dca" + "che_discard")]
     scalar_mem = re.compile("|".join(re.escape(w) for w in words), re.I)
     checked = 0
-    for f in sorted(os.listdir(KEYS_DIR)) + ["../../include/mldsa_keys.h", "../_keys_lib.py"]:
+    for f in sorted(os.listdir(KEYS_DIR)) + ["../../include/mldsa_keys.h", "../_keys_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
         path = os.path.normpath(os.path.join(KEYS_DIR, f))
         if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
             continue
@@ -212,4 +214,4 @@ def test_kernels_do_not_spill_and_sources_are_clean(keys):
         # plain C++ and the HIP atomic builtins only; no wave waits for another
         assert not re.search(r"\basm\b", t), f
         assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 4
+    assert checked >= 6

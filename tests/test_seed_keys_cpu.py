@@ -46,6 +46,7 @@ def test_a_clean_build_of_the_layer_produces_the_library_and_leaves_the_core_alo
     for f in ("Makefile", "seed.hip"):
         shutil.copy(os.path.join(SEED_DIR, f), shadow / f)
     os.symlink(build.CSRC, tmp_path / "fips204_amd" / "csrc")
+    os.symlink(os.path.join(os.path.dirname(SEED_DIR), "layer"), tmp_path / "fips204_amd" / "layer")
     os.symlink(os.path.join(ROOT, "include"), tmp_path / "include")
     assert not (shadow / "libmldsa_seed.so").exists()
     subprocess.run(["make", "-C", str(shadow)], check=True, capture_output=True)
@@ -54,6 +55,8 @@ def test_a_clean_build_of_the_layer_produces_the_library_and_leaves_the_core_alo
     subprocess.run(["make", "-C", str(shadow), "clean"], check=True, capture_output=True)
     assert not (shadow / "libmldsa_seed.so").exists() and not list(shadow.glob("*.res")) and not list(shadow.glob("*.o"))
     mk = open(os.path.join(SEED_DIR, "Makefile")).read()
+    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
+    mk += open(os.path.join(SEED_DIR, "..", "layer", "layer.mk")).read()
     assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
     assert "-Rpass-analysis=kernel-resource-usage" in mk
 
@@ -240,7 +243,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(seed):
         assert any(stem in nm for nm in kernels), stem
     assert sum("k_seed_tr" in nm for nm in kernels) == 3  # one per parameter set
     checked = 0
-    for f in sorted(os.listdir(SEED_DIR)) + ["../../include/mldsa_seed.h", "../_seed_lib.py"]:
+    for f in sorted(os.listdir(SEED_DIR)) + ["../../include/mldsa_seed.h", "../_seed_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
         path = os.path.normpath(os.path.join(SEED_DIR, f))
         if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
             continue
@@ -253,11 +256,13 @@ def test_kernels_do_not_spill_and_sources_are_clean(seed):
         # plain C++ only: every store is an ordinary vector store the compiler emits
         assert not re.search(r"\basm\b", t), f
         assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 4
+    assert checked >= 6
     # the core's device headers are included, never copied
     src = open(os.path.join(SEED_DIR, "seed.hip")).read()
+    assert '#include "../layer/layer_dev.h"' in src  # through the layers' shared device header: both links of the chain
+    dev = open(os.path.join(SEED_DIR, "..", "layer", "layer_dev.h")).read()
     for h in ("../csrc/keccak.h", "../csrc/field.h", "../csrc/rounding.h"):
-        assert f'#include "{h}"' in src
+        assert f'#include "{h}"' in dev
     # the comparison has one loop, whose bound is the key length, and leaves it by no other way
     cmp_src = src[src.index("void k_seed_cmp"):src.index("// ---", src.index("void k_seed_cmp"))]
     assert cmp_src.count("for (int c = lane; c < sk_vec; c += 64)") == 1 and "break" not in cmp_src and "__ballot" not in cmp_src
