@@ -19,6 +19,12 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _optr(t):
+    """_ptr for an argument the C ABI lets the caller leave out: None -> NULL.  A required tensor goes through _ptr, where None
+    fails in Python and never reaches the library as NULL."""
+    return C.c_void_p(0) if t is None else _ptr(t)
+
+
 def _stream(device=None):
     """torch's current stream ON `device` (None: the current device) as a hipStream_t.  Every call of a context must name a stream
     of the context's own device: with several GPUs in one process the current device is not necessarily that one."""
@@ -166,8 +172,10 @@ class HotPath:
         a = _polys(a, "a")
         out1 = torch.empty_like(a)
         out2 = torch.empty_like(a) if op <= 1 else None
-        _lib.check(self.lib.mldsa_rounding(self._h, pset, op, _ptr(a), _ptr(_polys(b, "b")) if b is not None else None, _ptr(out1),
-                                           _ptr(out2) if out2 is not None else None, a.numel() // N, _stream(self.device)))
+        if b is not None:
+            b = _polys(b, "b")
+        _lib.check(self.lib.mldsa_rounding(self._h, pset, op, _ptr(a), _optr(b), _ptr(out1), _optr(out2), a.numel() // N,
+                                           _stream(self.device)))
         return (out1, out2) if op <= 1 else out1
 
     # ---- codecs as seams (conversion.rs, encodings.rs); every `ok` is a uint8 tensor, 1 = the reference returns Ok
@@ -177,8 +185,9 @@ class HotPath:
         n = off.numel() - 1
         out = torch.empty((n, out_len), dtype=torch.uint8, device=off.device)
         bad = torch.empty(n, dtype=torch.uint8, device=off.device)
-        _lib.check(self.lib.mldsa_xof(self._h, bits, _ptr(data) if data is not None and data.numel() else None, _ptr(off), _ptr(out), out_len,
-                                      _ptr(bad), n, _stream(self.device)))
+        if data is not None and not data.numel():
+            data = None
+        _lib.check(self.lib.mldsa_xof(self._h, bits, _optr(data), _ptr(off), _ptr(out), out_len, _ptr(bad), n, _stream(self.device)))
         return out, bad
 
     def bit_pack(self, w, a, b):

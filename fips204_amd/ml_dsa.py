@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
-from .hotpath import HotPath, N, _ptr, _stream
+from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
 
@@ -151,12 +151,23 @@ def private_key_faults(pset, sk_bytes):
     return (over[:, :l * 256].any(axis=1) * _keycheck_lib.KEY_S1_RANGE + over[:, l * 256:].any(axis=1) * _keycheck_lib.KEY_S2_RANGE).astype(np.uint8)
 
 
-def _cat_with_offsets(items, device):
-    """list of bytes -> (uint8 device buffer, uint64 offsets[n + 1] on device)"""
+def _np_ptr(a):
+    """_optr for host memory: a numpy array's address, None -> NULL"""
+    return C.c_void_p(0) if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _cat(items):
+    """list of bytes -> (their bytes joined, uint64 offsets[n + 1]); b"\0" stands in for an empty buffer, so that what holds it
+    has an address"""
     lens = np.fromiter((len(b) for b in items), dtype=np.uint64, count=len(items))
     off = np.zeros(len(items) + 1, dtype=np.uint64)
     np.cumsum(lens, out=off[1:])
-    flat = b"".join(bytes(b) for b in items) or b"\0"
+    return b"".join(bytes(b) for b in items) or b"\0", off
+
+
+def _cat_with_offsets(items, device):
+    """list of bytes -> (uint8 device buffer, uint64 offsets[n + 1] on device)"""
+    flat, off = _cat(items)
     buf = torch.frombuffer(bytearray(flat), dtype=torch.uint8).to(device)
     return buf, torch.from_numpy(off.view(np.int64)).to(device)
 
@@ -192,6 +203,12 @@ class PrivateKeys:
             self.zeroize()
         except Exception:
             pass
+
+
+def _sk_ptrs(sks, ptr=_ptr):
+    """the fields of a PrivateKeys in the order every call of the C ABI takes them: rho, K, tr, s1, s2, t0.  ptr=_optr where a
+    missing field goes to the library as NULL (the slices of sign_group)."""
+    return (ptr(sks.rho), ptr(sks.cap_k), ptr(sks.tr), ptr(sks.s_1_hat_mont), ptr(sks.s_2_hat_mont), ptr(sks.t_0_hat_mont))
 
 
 def _check_key_idx(key_idx, n_keys, n_ops):
@@ -239,23 +256,43 @@ class MlDsa:
     def _verify_batch(self, pks, messages, sigs, ctxs, key_idx, run):
         """verify()'s host side around run(msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, key_idx)"""
         n_ops = len(messages)
-        wrong_len = None
-        if not isinstance(sigs, torch.Tensor):
-            wrong_len = np.array([len(s) != self.SIG_LEN for s in sigs], dtype=bool)
-            flat = b"".join(bytes(s) if len(s) == self.SIG_LEN else bytes(self.SIG_LEN) for s in sigs)
-            sigs = torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(self.device)
+        sigs, wrong_len = self._sig_rows(sigs)
+        msg_buf, msg_off, ctx_buf, ctx_off = self._stage_strings(messages, ctxs)
+        kidx = self._stage_key_idx(key_idx, len(pks), n_ops)
+        ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
+        run(msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, kidx)
+        return self._verdicts(ok, n_ops, wrong_len)
+
+    # ---- host side of the list-level device calls: each piece written once ----------------
+    def _stage_strings(self, messages, ctxs):
+        """messages and optional contexts (lists of byte strings) -> (msg_buf, msg_off, ctx_buf, ctx_off) on the device; no
+        contexts: ctx_buf = ctx_off = None"""
         msg_buf, msg_off = _cat_with_offsets(messages, self.device)
         ctx_buf = ctx_off = None
         if ctxs is not None:
             ctx_buf, ctx_off = _cat_with_offsets(ctxs, self.device)
-        if key_idx is None and len(pks) != n_ops:
-            key_idx = np.arange(n_ops, dtype=np.uint32) % len(pks)
-        key_idx = _check_key_idx(key_idx, len(pks), n_ops)
-        kidx = None
-        if key_idx is not None:
-            kidx = torch.as_tensor(key_idx.view(np.int32)).to(self.device)
-        ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
-        run(msg_buf, msg_off, sigs, ok, n_ops, ctx_buf, ctx_off, kidx)
+        return msg_buf, msg_off, ctx_buf, ctx_off
+
+    def _stage_key_idx(self, key_idx, n_keys, n_ops, wrap=True):
+        """key_idx checked (_check_key_idx) and uploaded as the int32 tensor the device calls take, or None.  wrap: without a
+        key_idx and with n_keys != n_ops, op i uses key i mod n_keys; wrap=False leaves fewer keys than ops to _check_key_idx,
+        which raises."""
+        if wrap and key_idx is None and n_keys != n_ops:
+            key_idx = np.arange(n_ops, dtype=np.uint32) % n_keys
+        key_idx = _check_key_idx(key_idx, n_keys, n_ops)
+        return None if key_idx is None else torch.as_tensor(key_idx.view(np.int32)).to(self.device)
+
+    def _sig_rows(self, sigs):
+        """signatures as verify takes them -> (uint8 device tensor, wrong_len).  A list is uploaded with zeros in place of every
+        signature of the wrong length and wrong_len marks those (bool array); a tensor passes through with wrong_len = None."""
+        if isinstance(sigs, torch.Tensor):
+            return sigs, None
+        wrong_len = np.array([len(s) != self.SIG_LEN for s in sigs], dtype=bool)
+        flat = b"".join(bytes(s) if len(s) == self.SIG_LEN else bytes(self.SIG_LEN) for s in sigs)
+        return torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(self.device), wrong_len
+
+    def _verdicts(self, ok, n_ops, wrong_len=None):
+        """waits for the device and reads ok[:n_ops] back as a bool array, False where _sig_rows found a wrong length"""
         torch.cuda.synchronize(self.device)
         res = ok[:n_ops].cpu().numpy().astype(bool)
         if wrong_len is not None:
@@ -280,24 +317,19 @@ class MlDsa:
     def verify_device(self, pks, msg_buf, msg_off, sigs, ok, n_ops, ctx_buf=None, ctx_off=None, key_idx=None,
                       mode=MODE_PURE, a_hat=None):
         """Same, everything already resident in HBM (what bench.py times)."""
-        null = C.c_void_p(0)
         fn, first = (self.lib.mldsa_verify, pks.rho) if a_hat is None else (self.lib.mldsa_verify_cached_a, a_hat)
         _lib.check(fn(
-            self.hp._h, self.pset, mode, _ptr(first), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks),
-            _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
-            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null,
-            _ptr(sigs), _ptr(ok), n_ops, _stream(self.device)))
+            self.hp._h, self.pset, mode, _ptr(first), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(key_idx),
+            _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf), _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops, _stream(self.device)))
         return ok
 
     def verify_pk_device(self, pk_bytes, msg_buf, msg_off, sigs, ok, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE):
         """mldsa_verify_pk: PublicKey::try_from_bytes + verify in one call -- pk_bytes = uint8 CUDA tensor [n_keys, PK_LEN] in wire format
         (key_idx None: op i uses key i).  Same verdicts as public_keys_from_bytes + verify_device."""
-        null = C.c_void_p(0)
         pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
         _lib.check(self.lib.mldsa_verify_pk(
-            self.hp._h, self.pset, mode, _ptr(pk), pk.shape[0], _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
-            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(sigs), _ptr(ok), n_ops,
-            _stream(self.device)))
+            self.hp._h, self.pset, mode, _ptr(pk), pk.shape[0], _optr(key_idx), _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf),
+            _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops, _stream(self.device)))
         return ok
 
     def verify_pk(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, mode=MODE_PURE, dedup=False):
@@ -305,21 +337,16 @@ class MlDsa:
         dedup=True: through verify_pk_dedup_device (equal keys are found on the device and expanded once); same verdicts."""
         n_ops = len(messages)
         pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
-        msg_buf, msg_off = _cat_with_offsets(messages, self.device)
-        ctx_buf = ctx_off = None
-        if ctxs is not None:
-            ctx_buf, ctx_off = _cat_with_offsets(ctxs, self.device)
-        kidx = _check_key_idx(key_idx, pk.shape[0], n_ops)
-        if kidx is not None:
-            kidx = torch.as_tensor(kidx.view(np.int32)).to(self.device)
+        msg_buf, msg_off, ctx_buf, ctx_off = self._stage_strings(messages, ctxs)
+        # stricter than verify: fewer keys than ops without a key_idx raises, and so does a signature of the wrong length
+        kidx = self._stage_key_idx(key_idx, pk.shape[0], n_ops, wrap=False)
         sg = self._key_bytes(sigs, self.SIG_LEN, "sigs") if n_ops else torch.zeros((1, self.SIG_LEN), dtype=torch.uint8, device=self.device)
         ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
         if dedup:
             self.verify_pk_dedup_device(pk, msg_buf, msg_off, sg, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
         else:
             self.verify_pk_device(pk, msg_buf, msg_off, sg, ok, n_ops, ctx_buf, ctx_off, kidx, mode)
-        torch.cuda.synchronize(self.device)
-        return ok[:n_ops].cpu().numpy().astype(bool)
+        return self._verdicts(ok, n_ops)
 
     # ---- equal wire-format keys found on the device (include/mldsa_keys.h) ------------
     @staticmethod
@@ -363,7 +390,7 @@ class MlDsa:
         on the table of distinct keys when there are at most max_cached_keys of them (None: DEDUP_MAX_CACHED_KEYS).  Waits once for
         the current stream (the number of distinct keys decides the route).  info: a dict that receives n_rows and route.
         scratch: the caller's own device scratch, a uint8 tensor from dedup_verify_scratch() (None: one is allocated for the call)."""
-        lib, null = _keys_lib.load(), C.c_void_p(0)
+        lib = _keys_lib.load()
         pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
         n_keys = pk.shape[0]
         n_dedup = n_keys if key_idx is not None else n_ops
@@ -375,9 +402,9 @@ class MlDsa:
             raise ValueError(f"scratch: {scratch.numel()} bytes, the call needs {nb}")
         out = _keys_lib.KeysInfo()
         _keys_lib.check(lib.mldsa_verify_pk_dedup(
-            self.hp._h, self.pset, mode, _ptr(pk), n_keys, _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
-            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(sigs), _ptr(ok), n_ops,
-            self._dedup_seed(seed), hash_bits, cap, _ptr(scratch), scratch.numel(), C.byref(out), _stream(self.device)))
+            self.hp._h, self.pset, mode, _ptr(pk), n_keys, _optr(key_idx), _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf),
+            _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops, self._dedup_seed(seed), hash_bits, cap, _ptr(scratch), scratch.numel(),
+            C.byref(out), _stream(self.device)))
         if info is not None:
             info["n_rows"], info["route"] = int(out.n_rows), ("cached" if out.route == _keys_lib.ROUTE_CACHED else "plain")
         return ok
@@ -419,8 +446,7 @@ class MlDsa:
         sk = self._key_bytes(sk_bytes, self.SK_LEN, "sk")
         n = sk.shape[0]
         o = out or self.empty_private_keys(n)
-        _lib.check(self.lib.mldsa_sk_expand(self.hp._h, self.pset, _ptr(sk), _ptr(o.rho), _ptr(o.cap_k), _ptr(o.tr), _ptr(o.s_1_hat_mont),
-                                            _ptr(o.s_2_hat_mont), _ptr(o.t_0_hat_mont), n, _stream(self.device)))
+        _lib.check(self.lib.mldsa_sk_expand(self.hp._h, self.pset, _ptr(sk), *_sk_ptrs(o), n, _stream(self.device)))
         return o
 
     def public_keys_into_bytes(self, pks):
@@ -434,9 +460,7 @@ class MlDsa:
         """PrivateKey::into_bytes for a batch (src/lib.rs:427-465): uint8 tensor [n, SK_LEN]"""
         n = len(sks)
         sk = torch.empty((n, self.SK_LEN), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.mldsa_sk_into_bytes(self.hp._h, self.pset, _ptr(sks.rho), _ptr(sks.cap_k), _ptr(sks.tr),
-                                                _ptr(sks.s_1_hat_mont), _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont), _ptr(sk), n,
-                                                _stream(self.device)))
+        _lib.check(self.lib.mldsa_sk_into_bytes(self.hp._h, self.pset, *_sk_ptrs(sks), _ptr(sk), n, _stream(self.device)))
         return sk
 
     def get_public_key(self, sks):
@@ -465,11 +489,8 @@ class MlDsa:
 
     @staticmethod
     def _cat_host(items):
-        lens = np.fromiter((len(b) for b in items), dtype=np.uint64, count=len(items))
-        off = np.zeros(len(items) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=off[1:])
-        flat = np.frombuffer(b"".join(bytes(b) for b in items) or b"\0", dtype=np.uint8)
-        return flat, off
+        flat, off = _cat(items)
+        return np.frombuffer(flat, dtype=np.uint8), off
 
     @staticmethod
     def _host_strings(items, n_ops, what):
@@ -502,10 +523,9 @@ class MlDsa:
             raise ValueError(f"{what}: a writable C-contiguous {np.dtype(dtype).name} array of at least {n_items} elements is required")
         return a
 
-    def verify_host(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, mode=MODE_PURE, out=None):
-        """mldsa_verify_host: wire-format public keys [n_keys, PK_LEN], signatures [n_ops, SIG_LEN] and messages
-        in HOST memory (numpy); returns a bool array.  `messages` / `ctxs`: list of byte strings, or a
-        (flat uint8 array, uint64 offsets[n + 1]) pair."""
+    def _verify_host_call(self, run, name, pk_bytes, messages, sigs, ctxs, key_idx, out):
+        """verify_host's body around run(pk, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, sigs, ok, n_ops): the library's call
+        with its handle, set and mode or ph in front of these, and its check.  name: the calling method, for messages."""
         pk = self._np_u8(pk_bytes, self.PK_LEN, "pk")
         sg = self._np_u8(sigs, self.SIG_LEN, "sigs")
         n_keys, n_ops = pk.size // self.PK_LEN, sg.size // self.SIG_LEN
@@ -515,15 +535,14 @@ class MlDsa:
             cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
         kidx = _check_key_idx(key_idx, n_keys, n_ops)
         # out: caller's (page-locked) uint8[n_ops]
-        ok = self._host_out(out, np.uint8, n_ops, "verify_host: out") if out is not None else np.zeros(max(n_ops, 1), dtype=np.uint8)
-        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
-        _lib.check(self._host_fn("verify")(self._host_handle(), self.pset, mode, vp(pk), n_keys, vp(kidx), vp(mflat), vp(moff), vp(cflat),
-                                           vp(coff), vp(sg), vp(ok), n_ops))
+        ok = self._host_out(out, np.uint8, n_ops, f"{name}: out") if out is not None else np.zeros(max(n_ops, 1), dtype=np.uint8)
+        run(_np_ptr(pk), n_keys, _np_ptr(kidx), _np_ptr(mflat), _np_ptr(moff), _np_ptr(cflat), _np_ptr(coff), _np_ptr(sg), _np_ptr(ok),
+            n_ops)
         return ok[:n_ops].astype(bool)
 
-    def sign_host(self, sk_bytes, messages, rnd, ctxs=None, key_idx=None, mode=MODE_PURE, out=None):
-        """mldsa_sign_host: wire-format private keys, messages and rnd in HOST memory; returns uint8 [n_ops, SIG_LEN].
-        out: (sig uint8[n_ops, SIG_LEN], status int32[n_ops]) buffers of the caller (page-locked ones are filled by DMA)."""
+    def _sign_host_call(self, run, name, alg, sk_bytes, messages, rnd, ctxs, key_idx, out):
+        """sign_host's body around run(sk, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, rnd, sigs, status, n_ops), as
+        _verify_host_call.  alg: "ML-DSA" or "HashML-DSA", for the message of a refused ctx."""
         sk = self._np_u8(sk_bytes, self.SK_LEN, "sk")
         rn = self._np_u8(rnd, 32, "rnd")
         n_keys, n_ops = sk.size // self.SK_LEN, rn.size // 32
@@ -534,20 +553,32 @@ class MlDsa:
         kidx = _check_key_idx(key_idx, n_keys, n_ops)
         if out is not None:
             if not isinstance(out, tuple) or len(out) != 2:
-                raise ValueError("sign_host: out = (sig uint8[n_ops, SIG_LEN], status int32[n_ops])")
-            sig = self._host_out(out[0], np.uint8, n_ops * self.SIG_LEN, "sign_host: out[0] (signatures)")
-            status = self._host_out(out[1], np.int32, n_ops, "sign_host: out[1] (status)")
+                raise ValueError(f"{name}: out = (sig uint8[n_ops, SIG_LEN], status int32[n_ops])")
+            sig = self._host_out(out[0], np.uint8, n_ops * self.SIG_LEN, f"{name}: out[0] (signatures)")
+            status = self._host_out(out[1], np.int32, n_ops, f"{name}: out[1] (status)")
             if sig.ndim == 2 and sig.shape[1] != self.SIG_LEN:
-                raise ValueError(f"sign_host: out[0] rows must be SIG_LEN = {self.SIG_LEN} bytes")
+                raise ValueError(f"{name}: out[0] rows must be SIG_LEN = {self.SIG_LEN} bytes")
             sig = sig.reshape(-1)[:n_ops * self.SIG_LEN].reshape(n_ops, self.SIG_LEN) if n_ops else sig
         else:
             sig, status = np.zeros((max(n_ops, 1), self.SIG_LEN), dtype=np.uint8), np.zeros(max(n_ops, 1), dtype=np.int32)
-        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
-        _lib.check(self._host_fn("sign")(self._host_handle(), self.pset, mode, vp(sk), n_keys, vp(kidx), vp(mflat), vp(moff), vp(cflat),
-                                         vp(coff), vp(rn), vp(sig), vp(status), n_ops))
+        run(_np_ptr(sk), n_keys, _np_ptr(kidx), _np_ptr(mflat), _np_ptr(moff), _np_ptr(cflat), _np_ptr(coff), _np_ptr(rn), _np_ptr(sig),
+            _np_ptr(status), n_ops)
         if n_ops and int(status[:n_ops].min()) < 0:
-            raise ValueError("ML-DSA.Sign: ctx too long")
+            raise ValueError(f"{alg}.Sign: ctx too long")
         return sig[:n_ops]
+
+    def verify_host(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, mode=MODE_PURE, out=None):
+        """mldsa_verify_host: wire-format public keys [n_keys, PK_LEN], signatures [n_ops, SIG_LEN] and messages
+        in HOST memory (numpy); returns a bool array.  `messages` / `ctxs`: list of byte strings, or a
+        (flat uint8 array, uint64 offsets[n + 1]) pair."""
+        return self._verify_host_call(lambda *a: _lib.check(self._host_fn("verify")(self._host_handle(), self.pset, mode, *a)),
+                                      "verify_host", pk_bytes, messages, sigs, ctxs, key_idx, out)
+
+    def sign_host(self, sk_bytes, messages, rnd, ctxs=None, key_idx=None, mode=MODE_PURE, out=None):
+        """mldsa_sign_host: wire-format private keys, messages and rnd in HOST memory; returns uint8 [n_ops, SIG_LEN].
+        out: (sig uint8[n_ops, SIG_LEN], status int32[n_ops]) buffers of the caller (page-locked ones are filled by DMA)."""
+        return self._sign_host_call(lambda *a: _lib.check(self._host_fn("sign")(self._host_handle(), self.pset, mode, *a)),
+                                    "sign_host", "ML-DSA", sk_bytes, messages, rnd, ctxs, key_idx, out)
 
     def keygen_host(self, xi, out=None):
         """mldsa_keygen_host: seeds [n, 32] in host memory -> (pk [n, PK_LEN], sk [n, SK_LEN]) numpy arrays.
@@ -562,8 +593,7 @@ class MlDsa:
         else:
             pk = np.zeros((max(n, 1), self.PK_LEN), dtype=np.uint8)
             sk = np.zeros((max(n, 1), self.SK_LEN), dtype=np.uint8)
-        vp = lambda a: C.c_void_p(a.ctypes.data)
-        _lib.check(self._host_fn("keygen")(self._host_handle(), self.pset, vp(x), vp(pk), vp(sk), n))
+        _lib.check(self._host_fn("keygen")(self._host_handle(), self.pset, _np_ptr(x), _np_ptr(pk), _np_ptr(sk), n))
         return pk[:n], sk[:n]
 
     # ---- KeyGen (src/traits.rs:8-114; src/lib.rs:247-250) ------------------------------
@@ -620,16 +650,8 @@ class MlDsa:
     def _sign_batch(self, sks, messages, rnd, ctxs, key_idx, run):
         """try_sign_with_seed()'s host side around run(msg_buf, msg_off, rnd, sigs, n_ops, ctx_buf, ctx_off, key_idx, status)"""
         n_ops = len(messages)
-        msg_buf, msg_off = _cat_with_offsets(messages, self.device)
-        ctx_buf = ctx_off = None
-        if ctxs is not None:
-            ctx_buf, ctx_off = _cat_with_offsets(ctxs, self.device)
-        if key_idx is None and len(sks) != n_ops:
-            key_idx = np.arange(n_ops, dtype=np.uint32) % len(sks)
-        key_idx = _check_key_idx(key_idx, len(sks), n_ops)
-        kidx = None
-        if key_idx is not None:
-            kidx = torch.as_tensor(key_idx.view(np.int32)).to(self.device)
+        msg_buf, msg_off, ctx_buf, ctx_off = self._stage_strings(messages, ctxs)
+        kidx = self._stage_key_idx(key_idx, len(sks), n_ops)
         rnd = self._key_bytes(rnd, 32, "rnd") if n_ops else torch.zeros((1, 32), dtype=torch.uint8, device=self.device)
         sigs = torch.empty((max(n_ops, 1), self.SIG_LEN), dtype=torch.uint8, device=self.device)
         status = torch.zeros(max(n_ops, 1), dtype=torch.int32, device=self.device)
@@ -661,17 +683,13 @@ class MlDsa:
         """Everything already resident in HBM (what bench.py times).  wait=False -> mldsa_sign_async: the call
         only enqueues; an op the enqueued rounds leave unfinished (p < 1e-9 per call) has status
         MLDSA_ERR_AGAIN and must be signed again."""
-        null = C.c_void_p(0)
         if a_hat is not None:
             fn, first = self.lib.mldsa_sign_cached_a, a_hat
         else:
             fn, first = (self.lib.mldsa_sign if wait else self.lib.mldsa_sign_async), sks.rho
         _lib.check(fn(
-            self.hp._h, self.pset, mode, _ptr(first), _ptr(sks.cap_k), _ptr(sks.tr), _ptr(sks.s_1_hat_mont),
-            _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont), len(sks), _ptr(key_idx) if key_idx is not None else null,
-            _ptr(msg_buf), _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
-            _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
-            _ptr(status) if status is not None else null, n_ops, _stream(self.device)))
+            self.hp._h, self.pset, mode, _ptr(first), *_sk_ptrs(sks)[1:], len(sks), _optr(key_idx), _ptr(msg_buf), _ptr(msg_off),
+            _optr(ctx_buf), _optr(ctx_off), _ptr(rnd), _ptr(sigs), _optr(status), n_ops, _stream(self.device)))
         return sigs
 
     # ---- HashML-DSA with the pre-hash on the device (include/mldsa_ph.h) ------------------
@@ -693,43 +711,38 @@ class MlDsa:
             raise ValueError(f"unknown ph {ph!r}")
         rows = torch.empty((max(n_ops, 1), rl), dtype=torch.uint8, device=self.device)
         bad = torch.empty(max(n_ops, 1), dtype=torch.uint8, device=self.device)
-        _ph_lib.check(lib.mldsa_prehash(self.hp._h, code, _ptr(msg_buf) if msg_buf is not None else C.c_void_p(0), _ptr(msg_off),
-                                        _ptr(rows), _ptr(bad), n_ops, _stream(self.device)))
+        _ph_lib.check(lib.mldsa_prehash(self.hp._h, code, _optr(msg_buf), _ptr(msg_off), _ptr(rows), _ptr(bad), n_ops,
+                                        _stream(self.device)))
         return rows[:n_ops], bad[:n_ops]
 
     def hash_verify_device(self, pks, msg_buf, msg_off, sigs, ok, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None):
         """mldsa_hash_verify: verify_device's arguments on RAW messages, the pre-hash `ph` computed on the device."""
-        null, code = C.c_void_p(0), self._ph_arg(ph)
+        code = self._ph_arg(ph)
         scratch = self._ph_scratch(code, n_ops)
         _ph_lib.check(_ph_lib.load().mldsa_hash_verify(
-            self.hp._h, self.pset, code, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks),
-            _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
-            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null,
-            _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            self.hp._h, self.pset, code, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(key_idx),
+            _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf), _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(),
+            _stream(self.device)))
         return ok
 
     def hash_verify_pk_device(self, pk_bytes, msg_buf, msg_off, sigs, ok, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None):
         """mldsa_hash_verify_pk: verify_pk_device's arguments (wire-format keys) on RAW messages, the pre-hash on the device."""
-        null, code = C.c_void_p(0), self._ph_arg(ph)
+        code = self._ph_arg(ph)
         pk = self._key_bytes(pk_bytes, self.PK_LEN, "pk")
         scratch = self._ph_scratch(code, n_ops)
         _ph_lib.check(_ph_lib.load().mldsa_hash_verify_pk(
-            self.hp._h, self.pset, code, _ptr(pk), pk.shape[0], _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf),
-            _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(sigs),
-            _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            self.hp._h, self.pset, code, _ptr(pk), pk.shape[0], _optr(key_idx), _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf),
+            _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return ok
 
     def hash_sign_device(self, sks, msg_buf, msg_off, rnd, sigs, n_ops, ph, ctx_buf=None, ctx_off=None, key_idx=None, status=None):
         """mldsa_hash_sign: sign_device's arguments on RAW messages, the pre-hash `ph` computed on the device.  Synchronous like
         mldsa_sign: signatures and statuses are final on return."""
-        null, code = C.c_void_p(0), self._ph_arg(ph)
+        code = self._ph_arg(ph)
         scratch = self._ph_scratch(code, n_ops)
         _ph_lib.check(_ph_lib.load().mldsa_hash_sign(
-            self.hp._h, self.pset, code, _ptr(sks.rho), _ptr(sks.cap_k), _ptr(sks.tr), _ptr(sks.s_1_hat_mont),
-            _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont), len(sks), _ptr(key_idx) if key_idx is not None else null,
-            _ptr(msg_buf), _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
-            _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
-            _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            self.hp._h, self.pset, code, *_sk_ptrs(sks), len(sks), _optr(key_idx), _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf),
+            _optr(ctx_off), _ptr(rnd), _ptr(sigs), _optr(status), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return sigs
 
 
@@ -738,14 +751,12 @@ class MlDsa:
         """mldsa_mu_compute: (mu [n_ops, 64] uint8, mu_flag [n_ops] int32) on the device, asynchronous on the current stream.
         tr: uint8 CUDA tensor [n_keys, 64] (the .tr of PublicKeys / PrivateKeys).  mu_flag: 0 hashed, 1 ctx longer than 255 bytes,
         2 malformed offsets or key index out of range; a flagged op's mu row is zero."""
-        null = C.c_void_p(0)
         tr = tr.contiguous().view(-1, 64)
         mu = torch.empty((max(n_ops, 1), _mu_lib.MU_LEN), dtype=torch.uint8, device=self.device)
         flag = torch.empty(max(n_ops, 1), dtype=torch.int32, device=self.device)
         _mu_lib.check(_mu_lib.load().mldsa_mu_compute(
-            self.hp._h, mode, _ptr(tr), tr.shape[0], _ptr(key_idx) if key_idx is not None else null,
-            _ptr(msg_buf) if msg_buf is not None else null, _ptr(msg_off), _ptr(ctx_buf) if ctx_buf is not None else null,
-            _ptr(ctx_off) if ctx_off is not None else null, _ptr(mu), _ptr(flag), n_ops, _stream(self.device)))
+            self.hp._h, mode, _ptr(tr), tr.shape[0], _optr(key_idx), _optr(msg_buf), _ptr(msg_off), _optr(ctx_buf), _optr(ctx_off),
+            _ptr(mu), _ptr(flag), n_ops, _stream(self.device)))
         return mu[:n_ops], flag[:n_ops]
 
     def mu_scratch(self, n_ops, sign=False):
@@ -758,53 +769,35 @@ class MlDsa:
     def verify_mu_device(self, pks, mu, sigs, ok, n_ops, key_idx=None, mu_flag=None, scratch=None):
         """mldsa_verify_mu: ML-DSA.Verify_internal from mu [n_ops, 64]; ok[op] = 1 iff accepted.  Asynchronous on the current
         stream.  scratch: a uint8 CUDA tensor from mu_scratch() (None: one is allocated for the call)."""
-        null = C.c_void_p(0)
         if scratch is None:
             scratch = self.mu_scratch(n_ops)
         _mu_lib.check(_mu_lib.load().mldsa_verify_mu(
-            self.hp._h, self.pset, _ptr(pks.rho), _ptr(pks.t1_d2_hat_mont), len(pks), _ptr(key_idx) if key_idx is not None else null,
-            _ptr(mu), _ptr(mu_flag) if mu_flag is not None else null, _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(),
-            _stream(self.device)))
+            self.hp._h, self.pset, _ptr(pks.rho), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(key_idx), _ptr(mu), _optr(mu_flag),
+            _ptr(sigs), _ptr(ok), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return ok
 
     def sign_mu_device(self, sks, mu, rnd, sigs, n_ops, key_idx=None, mu_flag=None, status=None, scratch=None):
         """mldsa_sign_mu: ML-DSA.Sign_internal from mu [n_ops, 64] and rnd [n_ops, 32]; blocks like sign_device, and the scratch is
         all zero when it returns."""
-        null = C.c_void_p(0)
         if scratch is None:
             scratch = self.mu_scratch(n_ops, sign=True)
         _mu_lib.check(_mu_lib.load().mldsa_sign_mu(
             self.hp._h, self.pset, _ptr(sks.rho), _ptr(sks.cap_k), _ptr(sks.s_1_hat_mont), _ptr(sks.s_2_hat_mont), _ptr(sks.t_0_hat_mont),
-            len(sks), _ptr(key_idx) if key_idx is not None else null, _ptr(mu), _ptr(mu_flag) if mu_flag is not None else null,
-            _ptr(rnd), _ptr(sigs), _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(),
-            _stream(self.device)))
+            len(sks), _optr(key_idx), _ptr(mu), _optr(mu_flag), _ptr(rnd), _ptr(sigs), _optr(status), n_ops, _ptr(scratch),
+            scratch.numel(), _stream(self.device)))
         return sigs
 
     def _mu_rows(self, mus, n_ops):
         return self._key_bytes(mus, _mu_lib.MU_LEN, "mu") if n_ops else torch.zeros((1, _mu_lib.MU_LEN), dtype=torch.uint8, device=self.device)
 
-    def _mu_key_idx(self, key_idx, n_keys, n_ops):
-        if key_idx is None and n_keys != n_ops:
-            key_idx = np.arange(n_ops, dtype=np.uint32) % n_keys
-        key_idx = _check_key_idx(key_idx, n_keys, n_ops)
-        return None if key_idx is None else torch.as_tensor(key_idx.view(np.int32)).to(self.device)
-
     def verify_mu(self, pks, mus, sigs, key_idx=None):
         """ML-DSA.Verify with an externally computed mu (external_mu) per operation: returns a bool array.  mus: list of 64-byte
         strings or a uint8 tensor [n_ops, 64]; sigs as for verify (a signature of the wrong length verifies as False)."""
         n_ops = len(mus)
-        wrong_len = None
-        if not isinstance(sigs, torch.Tensor):
-            wrong_len = np.array([len(s) != self.SIG_LEN for s in sigs], dtype=bool)
-            flat = b"".join(bytes(s) if len(s) == self.SIG_LEN else bytes(self.SIG_LEN) for s in sigs)
-            sigs = torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(self.device)
+        sigs, wrong_len = self._sig_rows(sigs)
         ok = torch.zeros(max(n_ops, 1), dtype=torch.uint8, device=self.device)
-        self.verify_mu_device(pks, self._mu_rows(mus, n_ops), sigs, ok, n_ops, self._mu_key_idx(key_idx, len(pks), n_ops))
-        torch.cuda.synchronize(self.device)
-        res = ok[:n_ops].cpu().numpy().astype(bool)
-        if wrong_len is not None:
-            res &= ~wrong_len
-        return res
+        self.verify_mu_device(pks, self._mu_rows(mus, n_ops), sigs, ok, n_ops, self._stage_key_idx(key_idx, len(pks), n_ops))
+        return self._verdicts(ok, n_ops, wrong_len)
 
     def try_sign_mu_with_seed(self, sks, mus, rnd, key_idx=None):
         """ML-DSA.Sign with an externally computed mu (external_mu) per operation and one 32-byte rnd each (zeros = deterministic):
@@ -813,7 +806,7 @@ class MlDsa:
         rnd = self._key_bytes(rnd, 32, "rnd") if n_ops else torch.zeros((1, 32), dtype=torch.uint8, device=self.device)
         sigs = torch.empty((max(n_ops, 1), self.SIG_LEN), dtype=torch.uint8, device=self.device)
         status = torch.zeros(max(n_ops, 1), dtype=torch.int32, device=self.device)
-        self.sign_mu_device(sks, self._mu_rows(mus, n_ops), rnd, sigs, n_ops, self._mu_key_idx(key_idx, len(sks), n_ops), status=status)
+        self.sign_mu_device(sks, self._mu_rows(mus, n_ops), rnd, sigs, n_ops, self._stage_key_idx(key_idx, len(sks), n_ops), status=status)
         if n_ops and int(status[:n_ops].min()) < 0:
             bad = int(np.flatnonzero(status[:n_ops].cpu().numpy() < 0)[0])
             raise ValueError(f"ML-DSA.Sign from mu: operation refused (op {bad})")
@@ -841,8 +834,7 @@ class MlDsa:
         if scratch is None:
             scratch = self.seed_scratch(n)
         _seed_lib.check(_seed_lib.load().mldsa_seed_expand(
-            self.hp._h, self.pset, _ptr(xi), _ptr(o.rho), _ptr(o.cap_k), _ptr(o.tr), _ptr(o.s_1_hat_mont), _ptr(o.s_2_hat_mont),
-            _ptr(o.t_0_hat_mont), _ptr(pk) if pk is not None else C.c_void_p(0), n, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            self.hp._h, self.pset, _ptr(xi), *_sk_ptrs(o), _optr(pk), n, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return (o, pk) if want_pk else o
 
     def check_seeds_device(self, xi, sk_bytes, scratch=None):
@@ -864,14 +856,12 @@ class MlDsa:
                                status=None, scratch=None):
         """mldsa_sign_seed: sign_device with the key table given as seeds xi (uint8 CUDA tensor [n_keys, 32]): the seeds are expanded
         once per call into the scratch, which is all zero when the call returns.  Blocks like sign_device."""
-        null = C.c_void_p(0)
         n_keys = xi.shape[0]
         if scratch is None:
             scratch = self.seed_scratch(n_keys, "sign")
         _seed_lib.check(_seed_lib.load().mldsa_sign_seed(
-            self.hp._h, self.pset, mode, _ptr(xi), n_keys, _ptr(key_idx) if key_idx is not None else null, _ptr(msg_buf), _ptr(msg_off),
-            _ptr(ctx_buf) if ctx_buf is not None else null, _ptr(ctx_off) if ctx_off is not None else null, _ptr(rnd), _ptr(sigs),
-            _ptr(status) if status is not None else null, n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            self.hp._h, self.pset, mode, _ptr(xi), n_keys, _optr(key_idx), _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf), _optr(ctx_off),
+            _ptr(rnd), _ptr(sigs), _optr(status), n_ops, _ptr(scratch), scratch.numel(), _stream(self.device)))
         return sigs
 
     def try_sign_from_seeds(self, xi, messages, rnd, ctxs=None, key_idx=None, mode=MODE_PURE):
@@ -927,8 +917,8 @@ class MlDsa:
         else:
             if scratch is None:
                 scratch = self.keycheck_scratch(n)
-            _keycheck_lib.check(lib.mldsa_keypair_check(self.hp._h, self.pset, _ptr(sk), _ptr(pk) if pk is not None else C.c_void_p(0),
-                                                        _ptr(flag), n, _ptr(scratch), scratch.numel(), _stream(self.device)))
+            _keycheck_lib.check(lib.mldsa_keypair_check(self.hp._h, self.pset, _ptr(sk), _optr(pk), _ptr(flag), n, _ptr(scratch),
+                                                        scratch.numel(), _stream(self.device)))
         return flag[:n]
 
     def private_keys_try_from_bytes(self, sk_bytes, pk_bytes=None, level="pair", out=None, scratch=None):
@@ -940,12 +930,10 @@ class MlDsa:
         n = sk.shape[0]
         o = out or self.empty_private_keys(n)
         flag = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
-        null = C.c_void_p(0)
         if lvl == _keycheck_lib.LEVEL_PAIR and scratch is None:
             scratch = self.keycheck_scratch(n)
         _keycheck_lib.check(_keycheck_lib.load().mldsa_sk_import(
-            self.hp._h, self.pset, lvl, _ptr(sk), _ptr(pk) if pk is not None else null, _ptr(o.rho), _ptr(o.cap_k), _ptr(o.tr),
-            _ptr(o.s_1_hat_mont), _ptr(o.s_2_hat_mont), _ptr(o.t_0_hat_mont), _ptr(flag), n, _ptr(scratch) if scratch is not None else null,
+            self.hp._h, self.pset, lvl, _ptr(sk), _optr(pk), *_sk_ptrs(o), _ptr(flag), n, _optr(scratch),
             scratch.numel() if scratch is not None else 0, _stream(self.device)))
         torch.cuda.synchronize(self.device)
         verdict = flag[:n].cpu().numpy()
@@ -974,48 +962,17 @@ class MlDsa:
         """mldsa_hash_verify_host: verify_host's arguments on RAW messages in host memory; the pre-hash `ph` is computed on the
         device while the message bytes stream through two staging chunks of `staging_bytes` (0 = the library's default)."""
         code = self._ph_arg(ph)
-        pk = self._np_u8(pk_bytes, self.PK_LEN, "pk")
-        sg = self._np_u8(sigs, self.SIG_LEN, "sigs")
-        n_keys, n_ops = pk.size // self.PK_LEN, sg.size // self.SIG_LEN
-        mflat, moff = self._host_strings(messages, n_ops, "messages")
-        cflat = coff = None
-        if ctxs is not None:
-            cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
-        kidx = _check_key_idx(key_idx, n_keys, n_ops)
-        ok = self._host_out(out, np.uint8, n_ops, "hash_verify_host: out") if out is not None else np.zeros(max(n_ops, 1), dtype=np.uint8)
-        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
-        _ph_lib.check(_ph_lib.load().mldsa_hash_verify_host(self._ph_host(staging_bytes), self.pset, code, vp(pk), n_keys, vp(kidx),
-                                                            vp(mflat), vp(moff), vp(cflat), vp(coff), vp(sg), vp(ok), n_ops))
-        return ok[:n_ops].astype(bool)
+        return self._verify_host_call(
+            lambda *a: _ph_lib.check(_ph_lib.load().mldsa_hash_verify_host(self._ph_host(staging_bytes), self.pset, code, *a)),
+            "hash_verify_host", pk_bytes, messages, sigs, ctxs, key_idx, out)
 
     def hash_sign_host(self, sk_bytes, messages, rnd, ctxs=None, ph=PH_SHA512, key_idx=None, out=None, staging_bytes=0):
         """mldsa_hash_sign_host: sign_host's arguments on RAW messages in host memory, the pre-hash `ph` on the device;
         returns uint8 [n_ops, SIG_LEN].  out: (sig uint8[n_ops, SIG_LEN], status int32[n_ops]) buffers of the caller."""
         code = self._ph_arg(ph)
-        sk = self._np_u8(sk_bytes, self.SK_LEN, "sk")
-        rn = self._np_u8(rnd, 32, "rnd")
-        n_keys, n_ops = sk.size // self.SK_LEN, rn.size // 32
-        mflat, moff = self._host_strings(messages, n_ops, "messages")
-        cflat = coff = None
-        if ctxs is not None:
-            cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
-        kidx = _check_key_idx(key_idx, n_keys, n_ops)
-        if out is not None:
-            if not isinstance(out, tuple) or len(out) != 2:
-                raise ValueError("hash_sign_host: out = (sig uint8[n_ops, SIG_LEN], status int32[n_ops])")
-            sig = self._host_out(out[0], np.uint8, n_ops * self.SIG_LEN, "hash_sign_host: out[0] (signatures)")
-            status = self._host_out(out[1], np.int32, n_ops, "hash_sign_host: out[1] (status)")
-            if sig.ndim == 2 and sig.shape[1] != self.SIG_LEN:
-                raise ValueError(f"hash_sign_host: out[0] rows must be SIG_LEN = {self.SIG_LEN} bytes")
-            sig = sig.reshape(-1)[:n_ops * self.SIG_LEN].reshape(n_ops, self.SIG_LEN) if n_ops else sig
-        else:
-            sig, status = np.zeros((max(n_ops, 1), self.SIG_LEN), dtype=np.uint8), np.zeros(max(n_ops, 1), dtype=np.int32)
-        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
-        _ph_lib.check(_ph_lib.load().mldsa_hash_sign_host(self._ph_host(staging_bytes), self.pset, code, vp(sk), n_keys, vp(kidx),
-                                                          vp(mflat), vp(moff), vp(cflat), vp(coff), vp(rn), vp(sig), vp(status), n_ops))
-        if n_ops and int(status[:n_ops].min()) < 0:
-            raise ValueError("HashML-DSA.Sign: ctx too long")
-        return sig[:n_ops]
+        return self._sign_host_call(
+            lambda *a: _ph_lib.check(_ph_lib.load().mldsa_hash_sign_host(self._ph_host(staging_bytes), self.pset, code, *a)),
+            "hash_sign_host", "HashML-DSA", sk_bytes, messages, rnd, ctxs, key_idx, out)
 
 
 class _PhHost:
@@ -1053,9 +1010,8 @@ class PrehashStream:
 
     def update(self, piece_buf, piece_off):
         """op i absorbs piece_buf[piece_off[i] : piece_off[i + 1]] (device tensors; piece_off: n_ops + 1 uint64 offsets)"""
-        _ph_lib.check(self.lib.mldsa_ph_update(self.m.hp._h, self.code, _ptr(self.state), self.state_bytes,
-                                               _ptr(piece_buf) if piece_buf is not None else C.c_void_p(0), _ptr(piece_off),
-                                               self.n_ops, _stream(self.m.device)))
+        _ph_lib.check(self.lib.mldsa_ph_update(self.m.hp._h, self.code, _ptr(self.state), self.state_bytes, _optr(piece_buf),
+                                               _ptr(piece_off), self.n_ops, _stream(self.m.device)))
         return self
 
     def final(self):
@@ -1123,10 +1079,6 @@ class MlDsaGroup(MlDsa):
         return MlDsa(self.pset, hotpath=h)
 
     @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-    @staticmethod
     def _slice_stream(t, stream):
         if stream is not None:
             return C.c_void_p(stream)
@@ -1139,9 +1091,9 @@ class MlDsaGroup(MlDsa):
         arr = (_lib.VerifySlice * len(self))()
         for i, sl in enumerate(slices):
             pks = sl["pks"]
-            arr[i] = _lib.VerifySlice(self._p(pks.rho), self._p(pks.tr), self._p(pks.t1_d2_hat_mont), len(pks), self._p(sl.get("key_idx")),
-                                      self._p(sl["msg_buf"]), self._p(sl["msg_off"]), self._p(sl.get("ctx_buf")), self._p(sl.get("ctx_off")),
-                                      self._p(sl["sigs"]), self._p(sl["ok"]), sl["n_ops"], self._slice_stream(sl["ok"], sl.get("stream")))
+            arr[i] = _lib.VerifySlice(_optr(pks.rho), _optr(pks.tr), _optr(pks.t1_d2_hat_mont), len(pks), _optr(sl.get("key_idx")),
+                                      _optr(sl["msg_buf"]), _optr(sl["msg_off"]), _optr(sl.get("ctx_buf")), _optr(sl.get("ctx_off")),
+                                      _optr(sl["sigs"]), _optr(sl["ok"]), sl["n_ops"], self._slice_stream(sl["ok"], sl.get("stream")))
         _lib.check(self.lib.mldsa_verify_group(self._g, self.pset, mode, arr, 1 if wait else 0))
 
     def sign_group(self, slices, mode=MODE_PURE, wait=True):
@@ -1150,17 +1102,16 @@ class MlDsaGroup(MlDsa):
         arr = (_lib.SignSlice * len(self))()
         for i, sl in enumerate(slices):
             sks = sl["sks"]
-            arr[i] = _lib.SignSlice(self._p(sks.rho), self._p(sks.cap_k), self._p(sks.tr), self._p(sks.s_1_hat_mont), self._p(sks.s_2_hat_mont),
-                                    self._p(sks.t_0_hat_mont), len(sks), self._p(sl.get("key_idx")), self._p(sl["msg_buf"]), self._p(sl["msg_off"]),
-                                    self._p(sl.get("ctx_buf")), self._p(sl.get("ctx_off")), self._p(sl["rnd"]), self._p(sl["sigs"]),
-                                    self._p(sl.get("status")), sl["n_ops"], self._slice_stream(sl["sigs"], sl.get("stream")))
+            arr[i] = _lib.SignSlice(*_sk_ptrs(sks, _optr), len(sks), _optr(sl.get("key_idx")), _optr(sl["msg_buf"]), _optr(sl["msg_off"]),
+                                    _optr(sl.get("ctx_buf")), _optr(sl.get("ctx_off")), _optr(sl["rnd"]), _optr(sl["sigs"]),
+                                    _optr(sl.get("status")), sl["n_ops"], self._slice_stream(sl["sigs"], sl.get("stream")))
         _lib.check(self.lib.mldsa_sign_group(self._g, self.pset, mode, arr, 1 if wait else 0))
 
     def keygen_group(self, slices, wait=True):
         """mldsa_keygen_group.  slices[i]: dict(xi, pk, sk, n_keys[, stream]), tensors on device i."""
         arr = (_lib.KeygenSlice * len(self))()
         for i, sl in enumerate(slices):
-            arr[i] = _lib.KeygenSlice(self._p(sl["xi"]), self._p(sl["pk"]), self._p(sl["sk"]), sl["n_keys"], self._slice_stream(sl["pk"], sl.get("stream")))
+            arr[i] = _lib.KeygenSlice(_optr(sl["xi"]), _optr(sl["pk"]), _optr(sl["sk"]), sl["n_keys"], self._slice_stream(sl["pk"], sl.get("stream")))
         _lib.check(self.lib.mldsa_keygen_group(self._g, self.pset, arr, 1 if wait else 0))
 
     def sync(self):

@@ -293,6 +293,16 @@ def test_verify_mu_acvp_sigver(sets, acvp_sigver):
     assert n == 45
 
 
+def test_verify_mu_wrong_length_signature_in_a_list(sets):
+    """as verify (tests/test_gpu_verify.py): a signature of the wrong length in a list is a False verdict, and one key serves both ops"""
+    m = sets[44]
+    pk, sk = orc.keygen_from_seed(44, bytes(32))
+    pks = m.public_keys_from_bytes([orc.pk_into_bytes(44, pk)])
+    mu = external_mu(host(pks.tr)[0].tobytes(), b"m")
+    sig = orc.sign_internal(44, sk, b"m", bytes(32), mode=0)
+    assert m.verify_mu(pks, [mu, mu], [sig, sig[:-1]]).tolist() == [True, False]
+
+
 # -------------------------------------------------------------------------------------------------------------- sign
 _SIGN = {}
 

@@ -104,4 +104,11 @@ def test_wrong_length_signature_and_empty_batch(sets):
     pks = upload_oracle_pks(m, [orc.pk_into_bytes(44, pk)])
     sig = orc.sign_internal(44, sk, b"m", bytes(32), mode=0)
     assert m.verify(pks, [b"m", b"m"], [sig, sig[:-1]], mode=0).tolist() == [True, False]
+    # verify_pk is the stricter importer: what verify answers with False, or covers by reusing the one key, raises there
+    pkb = [orc.pk_into_bytes(44, pk)]
+    assert m.verify_pk(pkb, [b"m", b"m"], [sig, sig], key_idx=[0, 0], mode=0).tolist() == [True, True]
+    with pytest.raises(ValueError, match="sigs: wrong length"):
+        m.verify_pk(pkb, [b"m", b"m"], [sig, sig[:-1]], key_idx=[0, 0], mode=0)
+    with pytest.raises(ValueError):
+        m.verify_pk(pkb, [b"m", b"m"], [sig, sig[:-1]], mode=0)
     assert m.verify(pks, [], [], mode=0).tolist() == []
