@@ -56,6 +56,182 @@ def test_host_entry_points_match_the_device_resident_path(sets, pinned):
     assert not m.verify_host(pk_h, msgs[:10], sig_h[:10], ctxs=long_ctx, key_idx=kidx[:10])[0]
 
 
+# ------------------------------------------------------------------------------ the sub-batch pipeline at small shapes
+# The test above needs 32 845 ops to reach three sub-batches.  With the sub-batch sizes lowered to 64 ops the same driver loop runs its
+# interesting shapes at 261 ops: five verify / key-generation sub-batches (64, 64, 64, 64, 5: the fourth takes slot 0 back while the
+# first one's downloads are pending, the last is ragged) and a signing cut of 197 + 64.
+N_SUB, NK_SUB, EDGE_OPS = 261, 6, (0, 63, 64, 260)
+MSG_LEN = {"short": None, "33k": 33 * 1024, "140k": 140 * 1024}  # one pack per call | one pack per sub-batch (> 8 MiB per call) | separate arrays
+
+
+@pytest.fixture(scope="module")
+def sub64():
+    """ML-DSA-44 on a context of its own whose *_host calls cut their batches every 64 ops"""
+    from fips204_amd.hotpath import HotPath
+    from fips204_amd.ml_dsa import MlDsa
+    env = {"MLDSA_TUNING_ENV": "1", "MLDSA_HOST_SUB_VERIFY": "64", "MLDSA_HOST_SUB_SIGN": "64"}
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        h2 = HotPath(0)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    try:
+        yield MlDsa(44, hotpath=h2)
+    finally:
+        h2.close()
+
+
+@pytest.fixture(scope="module")
+def sub64_ref(sub64):
+    """inputs of the 261-op cases and what the DEVICE-RESIDENT calls make of them, computed once per (message regime, key_idx, ctxs)
+    and never written to: ref(regime, with_kidx, with_ctx) -> dict"""
+    m, n = sub64, N_SUB
+    xi = [shake(b"s64-key", i) for i in range(n)]
+    pk_t, sk_t = m.keygen_from_seed(xi)
+    pk, sk = host(pk_t), host(sk_t)
+    rnd = [shake(b"s64-rnd", i) for i in range(n)]
+    rng = np.random.default_rng(64)
+    msgs = {"short": [shake(b"s64-msg", i, (i * 37) % 200) for i in range(n)]}
+    ctxs = [shake(b"s64-ctx", i, i % 9) for i in range(n)]
+    kidx = rng.integers(0, NK_SUB, n).astype(np.uint32)
+    cache = {}
+
+    def ref(regime, with_kidx, with_ctx):
+        key = (regime, with_kidx, with_ctx)
+        if key not in cache:
+            if regime not in msgs:
+                msgs[regime] = [rng.integers(0, 256, MSG_LEN[regime], dtype=np.uint8).tobytes() for _ in range(n)]
+            nk = NK_SUB if with_kidx else n
+            d = dict(xi=xi, rnd=rnd, msgs=msgs[regime], ctxs=ctxs if with_ctx else None, kidx=kidx if with_kidx else None, pk=pk[:nk], sk=sk[:nk],
+                     pks=m.public_keys_from_bytes(pk_t[:nk]), sks=m.private_keys_from_bytes(sk_t[:nk]))
+            d["sig"] = host(m.try_sign_with_seed(d["sks"], d["msgs"], rnd, ctxs=d["ctxs"], key_idx=d["kidx"]))
+            cache[key] = d
+        return cache[key]
+    ref.pk, ref.sk, ref.xi = pk, sk, xi
+    return ref
+
+
+def _host_array(a, pinned, keep):
+    """a private copy of `a` in pageable or in page-locked host memory"""
+    a = np.ascontiguousarray(a)
+    if not pinned:
+        return a.copy()
+    t = torch.empty(max(a.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    keep.append(t)
+    v = t.numpy()[:a.nbytes].view(a.dtype).reshape(a.shape)
+    v[...] = a
+    return v
+
+
+def _host_inputs(m, d, pinned, keep):
+    mflat, moff = m._cat_host(d["msgs"])
+    c = None
+    if d["ctxs"] is not None:
+        cflat, coff = m._cat_host(d["ctxs"])
+        c = (_host_array(cflat, pinned, keep), _host_array(coff, pinned, keep))
+    kidx = _host_array(d["kidx"], pinned, keep) if d["kidx"] is not None else None
+    return (_host_array(mflat, pinned, keep), _host_array(moff, pinned, keep)), c, kidx
+
+
+def _key_of(d, i):
+    return int(d["kidx"][i]) if d["kidx"] is not None else i
+
+
+def _no_secret_left(m):
+    scanned, nonzero = m.hp.secret_residue()  # mldsa_debug_secret_residue, as tests/test_gpu_zeroise.py reads it
+    assert scanned > 0 and nonzero == 0, f"{nonzero} non-zero bytes of {scanned} left in the staging buffers"
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+def test_keygen_host_in_five_sub_batches(sub64, sub64_ref, pinned):
+    """mldsa_keygen_host, 261 keys in sub-batches of 64, 64, 64, 64, 5: the fourth takes slot 0 back with the first one's two
+    downloads (pk, sk) pending -- with pageable outputs the bounce copies made at reclaim -- and the last is ragged.  Every byte
+    equals the device-resident call's, keys 0, 63, 64, 260 the oracle's, and no seed or private key stays in the staging buffers."""
+    m, n, keep = sub64, N_SUB, []
+    xi = _host_array(np.frombuffer(b"".join(sub64_ref.xi), dtype=np.uint8).reshape(n, 32), pinned, keep)
+    out = None
+    if pinned:
+        out = (_pinned((n, m.PK_LEN), np.uint8)[1], _pinned((n, m.SK_LEN), np.uint8)[1])
+        keep.append(out)
+    pk_h, sk_h = m.keygen_host(xi, out=out)
+    _no_secret_left(m)
+    assert np.array_equal(pk_h, sub64_ref.pk) and np.array_equal(sk_h, sub64_ref.sk)
+    for i in EDGE_OPS:
+        pk_o, sk_o = orc.keygen_from_seed(44, sub64_ref.xi[i])
+        assert pk_h[i].tobytes() == orc.pk_into_bytes(44, pk_o) and sk_h[i].tobytes() == orc.sk_into_bytes(44, sk_o), i
+
+
+@pytest.mark.parametrize("with_ctx", [True, False])
+@pytest.mark.parametrize("with_kidx", [True, False])
+@pytest.mark.parametrize("regime", ["short", "33k", "140k"])
+@pytest.mark.parametrize("pinned", [False, True])
+def test_verify_host_in_five_sub_batches(sub64, sub64_ref, pinned, regime, with_kidx, with_ctx):
+    """mldsa_verify_host, 261 ops in five sub-batches, in the three ways the side inputs travel: short messages (the whole call's in one
+    pack, uploaded once after the first sub-batch's signatures), 33 KiB messages (the call's side bytes exceed the 8 MiB pack limit: one
+    pack per sub-batch) and 140 KiB messages (a 64-op sub-batch exceeds it: five separate arrays); with key_idx over 6 keys and without
+    (op i under key i: sub-batch j reads the key table from row 64 j on); with ctxs of 0 ... 8 bytes and with none.  One flipped byte in
+    the signatures of ops 3, 63, 64, 260: exactly those verdicts are false, as the device-resident call and the oracle say."""
+    m, n, keep = sub64, N_SUB, []
+    d = sub64_ref(regime, with_kidx, with_ctx)
+    bad = [3, 63, 64, 260]
+    sig_c = d["sig"].copy()
+    for i in bad:
+        sig_c[i, 7 + i % 20] ^= 0x20  # inside c~: the challenge no longer matches
+    mh, ch, kh = _host_inputs(m, d, pinned, keep)
+    ok_h = m.verify_host(_host_array(d["pk"], pinned, keep), mh, _host_array(sig_c, pinned, keep), ctxs=ch, key_idx=kh)
+    ok_d = m.verify(d["pks"], d["msgs"], torch.from_numpy(sig_c).cuda(), ctxs=d["ctxs"], key_idx=d["kidx"])
+    want = np.ones(n, dtype=bool)
+    want[bad] = False
+    assert np.array_equal(ok_h, ok_d) and np.array_equal(ok_h, want), np.nonzero(ok_h != want)[0]
+    for i in EDGE_OPS:
+        pk_o = orc.pk_try_from_bytes(44, d["pk"][_key_of(d, i)].tobytes())
+        ctx = d["ctxs"][i] if with_ctx else b""
+        assert bool(orc.verify_internal(44, pk_o, d["msgs"][i], sig_c[i].tobytes(), ctx=ctx, mode=0)) == bool(ok_h[i]), i
+
+
+@pytest.mark.parametrize("with_kidx", [True, False])
+@pytest.mark.parametrize("regime", ["short", "140k"])
+@pytest.mark.parametrize("pinned", [False, True])
+def test_sign_host_in_two_sub_batches(sub64, sub64_ref, pinned, regime, with_kidx):
+    """mldsa_sign_host, 261 ops on the sub-batch leg (pageable output; in the page-locked run only the inputs are page-locked), cut 197 + 64:
+    two slots with two downloads each (signatures, statuses).  Short messages go up packed, a 197-op sub-batch of 140 KiB messages as
+    separate arrays; with key_idx over 6 keys and with op i under key i.  Every byte equals the device-resident call's, ops 0, 63, 64,
+    260 the oracle's, and no private key or rnd stays in the staging buffers."""
+    m, n, keep = sub64, N_SUB, []
+    d = sub64_ref(regime, with_kidx, True)
+    mh, ch, kh = _host_inputs(m, d, pinned, keep)
+    rnd = _host_array(np.frombuffer(b"".join(d["rnd"]), dtype=np.uint8).reshape(n, 32), pinned, keep)
+    sig, st = np.full((n, m.SIG_LEN), 0xA5, dtype=np.uint8), np.full(n, -7, dtype=np.int32)
+    got = m.sign_host(_host_array(d["sk"], pinned, keep), mh, rnd, ctxs=ch, key_idx=kh, out=(sig, st))
+    _no_secret_left(m)
+    assert got.ctypes.data == sig.ctypes.data and np.array_equal(sig, d["sig"]) and not st.any()
+    for i in EDGE_OPS:
+        sk_o = orc.sk_try_from_bytes(44, d["sk"][_key_of(d, i)].tobytes())
+        assert sig[i].tobytes() == orc.sign_internal(44, sk_o, d["msgs"][i], d["rnd"][i], ctx=d["ctxs"][i], mode=0), i
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+def test_sign_host_sub_batches_refuse_an_over_long_ctx_per_op(sub64, sub64_ref, pinned):
+    """an over-long ctx at ops 1, 197 and 260 -- in the first sub-batch, first and last of the second: the call raises, those three rows
+    are zero with status -2, every other row is the device-resident call's, and the staging buffers are cleared on this way out too"""
+    m, n, keep = sub64, N_SUB, []
+    d = dict(sub64_ref("short", True, True))
+    bad = [1, 197, 260]
+    d["ctxs"] = [b"z" * 256 if i in bad else c for i, c in enumerate(d["ctxs"])]
+    mh, ch, kh = _host_inputs(m, d, pinned, keep)
+    rnd = _host_array(np.frombuffer(b"".join(d["rnd"]), dtype=np.uint8).reshape(n, 32), pinned, keep)
+    sig, st = np.full((n, m.SIG_LEN), 0xA5, dtype=np.uint8), np.full(n, -7, dtype=np.int32)
+    with pytest.raises(ValueError):
+        m.sign_host(_host_array(d["sk"], pinned, keep), mh, rnd, ctxs=ch, key_idx=kh, out=(sig, st))
+    _no_secret_left(m)
+    good = np.ones(n, dtype=bool)
+    good[bad] = False
+    assert np.array_equal(sig[good], d["sig"][good]) and not sig[bad].any()
+    assert (st[bad] == -2).all() and not st[good].any()
+
+
 # ------------------------------------------------------------------------------ HashML-DSA (pre-hash) front-end
 @pytest.mark.parametrize("pset", [44, 65, 87])
 def test_hash_sign_and_hash_verify_match_the_oracle(sets, pset):
