@@ -56,6 +56,10 @@ def test_sign_graph_replay_async_and_extra_rounds_are_bit_identical(hp, sets, ps
         s, stat = host(sig), host(st)
         again = stat == -5
         assert 0 < again.sum() < n and (stat[~again] == 0).all()
+        # exactly the ops whose loop takes more than the 2 candidates the plan tests (the oracle's iteration counts; tests/long_tail_cases.py)
+        sk_o = [orc.sk_try_from_bytes(pset, row.tobytes()) for row in host(b["sk"])]
+        _, iters, _ = orc.sign_trace_batch_mt(pset, sk_o, b["kidx_host"], b["msgs"], b["rnd"], min(16, os.cpu_count() or 1), mode=0, cap=1)
+        assert np.array_equal(again, iters > 2), np.nonzero(again != (iters > 2))[0]
         assert not s[again].any()
         assert np.array_equal(s[~again], direct[~again])
     finally:
