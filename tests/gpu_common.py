@@ -1,6 +1,11 @@
-"""Fixtures and helpers shared by the component-wise GPU test files (test_gpu_keys / _boundary / _group / _host_api / _sign_schedule / _seams /
-_baseline_configs): one context per test module, the three parameter sets on it, byte-string derivation, device upload helpers, the
-offset-table corruptions and the fuzz-derived batches.  Import with `from gpu_common import *`."""
+"""Fixtures and helpers shared by the GPU test files: one context per test module, the three parameter sets on it, byte-string derivation,
+device upload helpers, pre-filled scratch and the count of its non-zero bytes, host memory from the library's allocator, the
+offset-table corruptions and the fuzz-derived batches.
+
+Imported whole (`from gpu_common import *`) by test_gpu_keys / _boundary / _group / _host_api / _sign_schedule / _seams /
+_baseline_configs / _prehash / _prehash_stream / _prehash_fips_list / _keys_dedup / _external_mu / _seed_keys / _keycheck / _ct0_bound /
+_sign_long_tail / _rare_sampler_paths, and by name (`hp`, `host`, `dev` where theirs were the same) by test_gpu_poly / _samplers /
+_codec_seams / _sign_keygen / _stress / _batcher."""
 import ctypes as C  # noqa: F401
 import hashlib
 import os  # noqa: F401
@@ -38,6 +43,29 @@ def dev(a):
 
 def dev_off(off):
     return torch.from_numpy(np.ascontiguousarray(off, dtype=np.uint64).view(np.int64)).cuda()
+
+def kidx_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
+
+def filled(nbytes):
+    """a scratch pre-filled so that stale bytes would show"""
+    return torch.full((max(nbytes, 256),), 0x5A, dtype=torch.uint8, device="cuda")
+
+def nonzero_bytes(m, t):
+    from fips204_amd import _lib
+    from fips204_amd.hotpath import _ptr
+    torch.cuda.synchronize()
+    nz = C.c_size_t()
+    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
+    return nz.value
+
+def _host_alloc(m, a):
+    """a copy of the uint8 array `a` in memory from mldsa_host_alloc: (handle to free, numpy view)"""
+    p = C.c_void_p()
+    assert m.lib.mldsa_host_alloc(C.byref(p), max(a.size, 1)) == 0
+    v = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(a.size, 1),))[:a.size]
+    v[:] = a
+    return p, v
 
 def table(items):
     off = np.zeros(len(items) + 1, dtype=np.uint64)
@@ -152,4 +180,4 @@ def _pinned(shape, dtype):
     return t, a
 
 
-__all__ = ['C', 'hashlib', 'os', 'threading', 'time', 'np', 'pytest', 'torch', 'PSET', 'orc', 'hp', 'sets', 'host', 'shake', 'dev', 'dev_off', 'table', 'pairs_ok', 'corruptions', 'make_batch', 'oracle_sigs', 'CLASSES', 'fuzz_batch', '_pinned']
+__all__ = ['C', 'hashlib', 'os', 'threading', 'time', 'np', 'pytest', 'torch', 'PSET', 'orc', 'hp', 'sets', 'host', 'shake', 'dev', 'dev_off', 'kidx_dev', 'filled', 'nonzero_bytes', '_host_alloc', 'table', 'pairs_ok', 'corruptions', 'make_batch', 'oracle_sigs', 'CLASSES', 'fuzz_batch', '_pinned']

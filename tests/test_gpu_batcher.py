@@ -10,17 +10,10 @@ import pytest
 
 from fips204_amd import _lib
 from fips204_amd.ml_dsa import MODE_INTERNAL, MODE_PREHASH, MODE_PURE, MlDsaBatcher
+from gpu_common import hp  # noqa: F401
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hp():
-    from fips204_amd.hotpath import HotPath
-    h = HotPath(0)
-    yield h
-    h.close()
 
 
 def requests_for(pset, n, n_keys, seed):

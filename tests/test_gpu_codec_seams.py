@@ -10,6 +10,7 @@ import torch
 
 from fips204_amd import _lib
 from fips204_amd.hotpath import HotPath
+from gpu_common import dev, host
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -19,15 +20,6 @@ N = 256
 @pytest.fixture(scope="module")
 def hp():
     return HotPath(0)
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True)).cuda()
 
 
 # (a, b) pairs the reference packs with: t1 (encodings.rs:38), eta (137-150), t0 (155-160), z (266), w1 (354), and the 6-bit

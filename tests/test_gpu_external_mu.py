@@ -1,7 +1,7 @@
 """External-mu ML-DSA on the device (include/mldsa_mu.h): mldsa_mu_compute against hashlib, mldsa_verify_mu against mldsa_verify and
 the oracle, mldsa_sign_mu against the oracle and mldsa_sign byte for byte, across passes, compactions, refusals and streams."""
 from gpu_common import *  # noqa: F401,F403
-from gpu_common import C, corruptions, dev, dev_off, fuzz_batch, hashlib, host, np, orc, pairs_ok, pytest, table, torch
+from gpu_common import C, corruptions, dev, dev_off, fuzz_batch, hashlib, host, kidx_dev, nonzero_bytes, np, orc, pairs_ok, pytest, table, torch
 
 from conftest import PSET
 from fips204_amd import _lib, _mu_lib
@@ -23,22 +23,11 @@ def u8(rows, width):
     return torch.frombuffer(bytearray(b"".join(rows) or bytes(width)), dtype=torch.uint8).cuda().view(-1, width)
 
 
-def kidx_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
 def scratch_for(m, n, sign=False):
     """a scratch of exactly one pass over n ops, pre-filled so that stale bytes would show"""
     lib = _mu_lib.load()
     nb = (lib.mldsa_mu_sign_scratch_bytes if sign else lib.mldsa_mu_verify_scratch_bytes)(m.pset, n)
     return torch.full((nb,), 0x5A, dtype=torch.uint8, device="cuda")
-
-
-def nonzero_bytes(m, t):
-    torch.cuda.synchronize()
-    nz = C.c_size_t()
-    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
-    return nz.value
 
 
 # ---------------------------------------------------------------------------------------------------------------- mu

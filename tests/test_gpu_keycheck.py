@@ -3,7 +3,7 @@ mldsa_sk_import against the restatement of tests/keycheck_cases.py -- the ACVP k
 neighbours, with and without pk, across passes, refusals and streams, the zeroed scratch behind each call -- and the Python layer on
 top.  Every test runs for the three sets at n = 1 (one key), 64 (one full minimum pass) and 65 (the pass boundary)."""
 from gpu_common import *  # noqa: F401,F403
-from gpu_common import C, host, np, orc, pytest, shake, torch
+from gpu_common import C, filled, host, nonzero_bytes, np, orc, pytest, shake, torch
 
 import keycheck_cases as kc
 from fips204_amd import _keycheck_lib, _lib
@@ -33,18 +33,6 @@ def rows(keys):
 
 def scratch_bytes(m, n):
     return lib().mldsa_keycheck_scratch_bytes(m.pset, n)
-
-
-def filled(nbytes):
-    """a scratch pre-filled so that stale bytes would show"""
-    return torch.full((max(nbytes, 256),), 0x5A, dtype=torch.uint8, device="cuda")
-
-
-def nonzero_bytes(m, t):
-    torch.cuda.synchronize()
-    nz = C.c_size_t()
-    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
-    return nz.value
 
 
 def flags_out(n):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import host, hp  # noqa: F401
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -12,21 +13,8 @@ Q = orc.Q
 SETS = {44: (4, 4, 2, 1 << 17), 65: (6, 5, 4, 1 << 19), 87: (8, 7, 2, 1 << 19)}
 
 
-@pytest.fixture(scope="module")
-def hp():
-    from fips204_amd.hotpath import HotPath
-    h = HotPath(0)
-    yield h
-    h.close()
-
-
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def ntt_inputs(rng):

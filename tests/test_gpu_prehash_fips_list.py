@@ -272,14 +272,6 @@ def test_incremental_65536_ops_and_sticky_refusals(sets, ph):
         assert rows[i].tobytes() == cases.own_row(parts[0][i] + named[i] + parts[2][i], ph), (ph, i)
 
 
-def _host_alloc(m, a):
-    p = C.c_void_p()
-    assert m.lib.mldsa_host_alloc(C.byref(p), max(a.size, 1)) == 0
-    v = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(a.size, 1),))[:a.size]
-    v[:] = a
-    return p, v
-
-
 @pytest.mark.parametrize("pset", [44, 65, 87])
 def test_hash_host_calls_match_the_host_prehash_route(sets, pset):
     """messages, keys and signatures in host memory, staging smaller than the largest message and the default, pageable and

@@ -144,15 +144,6 @@ def test_stream_refusals_are_per_op_sticky_and_stay_inside_state_and_pieces(sets
     assert lib.mldsa_ph_final(m.hp._h, code, sptr, nb, NULL, NULL, NULL, n, strm) == _lib.ERR_PARAM
 
 
-def _host_alloc(m, a):
-    """a copy of the uint8 array `a` in memory from mldsa_host_alloc: (handle to free, numpy view)"""
-    p = C.c_void_p()
-    assert m.lib.mldsa_host_alloc(C.byref(p), max(a.size, 1)) == 0
-    v = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(a.size, 1),))[:a.size]
-    v[:] = a
-    return p, v
-
-
 HOST_LENS = (0, 1, 63, 64, 65, 167, 168, 4095, 4096, 4097, 5000, 12289, 200 << 10, 3, 9000, 128, 100, 2, 70000, 31, 8192, 777, 1, 0)
 STAGINGS = (4096, 64 << 20, 0)
 

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import host, hp  # noqa: F401
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -10,21 +11,8 @@ pytestmark = pytest.mark.gpu
 SETS = {44: (4, 4, 2, 1 << 17, 39, 32), 65: (6, 5, 4, 1 << 19, 49, 48), 87: (8, 7, 2, 1 << 19, 60, 64)}
 
 
-@pytest.fixture(scope="module")
-def hp():
-    from fips204_amd.hotpath import HotPath
-    h = HotPath(0)
-    yield h
-    h.close()
-
-
 def devb(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 @pytest.mark.parametrize("pset", [44, 65, 87])

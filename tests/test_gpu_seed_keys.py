@@ -2,7 +2,7 @@
 mldsa_keygen -> mldsa_sk_expand field by field, mldsa_seed_check on damaged keys and seeds, mldsa_sign_seed against mldsa_sign byte for
 byte, across passes, refusals and streams, the zeroed scratch behind each of them, and the Python layer on top."""
 from gpu_common import *  # noqa: F401,F403
-from gpu_common import C, dev, dev_off, hashlib, host, np, orc, pytest, shake, table, torch
+from gpu_common import C, dev, dev_off, filled, hashlib, host, kidx_dev, nonzero_bytes, np, orc, pytest, shake, table, torch
 
 from conftest import PSET
 from fips204_amd import _lib, _seed_lib
@@ -21,26 +21,10 @@ def u8(rows, width):
     return torch.frombuffer(bytearray(b"".join(rows) or bytes(width)), dtype=torch.uint8).cuda().view(-1, width)
 
 
-def kidx_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
 def scratch_bytes(m, n, what="expand"):
     lib = _seed_lib.load()
     return {"expand": lib.mldsa_seed_expand_scratch_bytes, "check": lib.mldsa_seed_check_scratch_bytes,
             "sign": lib.mldsa_seed_sign_scratch_bytes}[what](m.pset, n)
-
-
-def filled(nbytes):
-    """a scratch pre-filled so that stale bytes would show"""
-    return torch.full((max(nbytes, 256),), 0x5A, dtype=torch.uint8, device="cuda")
-
-
-def nonzero_bytes(m, t):
-    torch.cuda.synchronize()
-    nz = C.c_size_t()
-    _lib.check(m.lib.mldsa_debug_count_nonzero(_ptr(t), t.numel(), C.byref(nz)))
-    return nz.value
 
 
 # ------------------------------------------------------------------------------------------------- the parent route, once per set

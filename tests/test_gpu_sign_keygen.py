@@ -7,6 +7,7 @@ import torch
 
 from chacha8rng import ChaCha8Rng
 from conftest import PSET
+from gpu_common import host
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -20,11 +21,6 @@ def sets():
     hp = HotPath(0)
     yield {s: MlDsa(s, hotpath=hp) for s in (44, 65, 87)}
     hp.close()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def test_acvp_keygen(sets, acvp_keygen):  # nist_vectors/mod.rs:56-92

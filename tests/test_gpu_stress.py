@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import host
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -16,11 +17,6 @@ def sets():
     hp = HotPath(0)
     yield {s: MlDsa(s, hotpath=hp) for s in (44, 65, 87)}
     hp.close()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 @pytest.mark.parametrize("pset", [44, 65, 87])

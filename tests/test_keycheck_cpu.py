@@ -3,98 +3,42 @@ clean build produces it and leaves the core untouched, its C ABI, how it is link
 argument checks, its kernels' resources and sources -- and the expected verdicts the device tests compare against: the restatement of
 tests/keycheck_cases.py on the ACVP keyGen vectors and on every damage class, and the host helper private_key_faults against a second
 decode."""
-import ctypes as C
-import glob
-import hashlib
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import keycheck_cases as kc
 from fips204_amd import _keycheck_lib, _lib
+from layer_checks import (KL, ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, includes_the_core_device_headers,
+                          kernel_resources, layered_on_core, scratch_sweep, sources_clean)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KC_DIR = os.path.join(ROOT, "fips204_amd", "keycheck")
-KL = {44: (4, 4), 65: (6, 5), 87: (8, 7)}  # set -> K, L
-PK_SK = {44: (1312, 2560), 65: (1952, 4032), 87: (2592, 4896)}
 EXPORTS = {"mldsa_keycheck_abi_version", "mldsa_keycheck_last_error", "mldsa_keycheck_scratch_bytes", "mldsa_sk_range_check",
            "mldsa_keypair_check", "mldsa_sk_import"}
 
 
-def _sha(path):
-    return hashlib.sha256(open(path, "rb").read()).hexdigest()
-
-
 @pytest.fixture(scope="module")
 def keycheck():
-    if not os.path.exists(_keycheck_lib.LIB_PATH) or not glob.glob(os.path.join(KC_DIR, "*.res")):
-        from fips204_amd import build
-        build.build()
-    return _keycheck_lib.load()
+    return built(_keycheck_lib, KC_DIR)
 
 
 def test_a_clean_build_of_the_layer_produces_the_library_and_leaves_the_core_alone(keycheck, tmp_path):
-    """The layer is compiled from scratch in a shadow of the tree (its own Makefile and source copied, the core's directory and
-    include/ linked), so a failure half way leaves the checkout's libmldsa_keycheck.so in place for the tests that follow."""
     from fips204_amd import build
     assert build.KEYCHECK_LIB == _keycheck_lib.LIB_PATH
-    before = _sha(build.LIB)
-    build.build()  # the whole chain, as a checkout runs it: everything is up to date, so nothing is recompiled
-    for lib in (build.LIB, build.PH_LIB, build.KEYS_LIB, build.MU_LIB, build.SEED_LIB, build.KEYCHECK_LIB):
-        assert os.path.exists(lib), lib  # the six libraries of a checkout
-    assert _sha(build.LIB) == before, "build() changed libmldsa_hip.so"
-    shadow = tmp_path / "fips204_amd" / "keycheck"
-    shadow.mkdir(parents=True)
-    for f in ("Makefile", "keycheck.hip"):
-        shutil.copy(os.path.join(KC_DIR, f), shadow / f)
-    os.symlink(build.CSRC, tmp_path / "fips204_amd" / "csrc")
-    os.symlink(os.path.join(os.path.dirname(KC_DIR), "layer"), tmp_path / "fips204_amd" / "layer")
-    os.symlink(os.path.join(ROOT, "include"), tmp_path / "include")
-    assert not (shadow / "libmldsa_keycheck.so").exists()
-    subprocess.run(["make", "-C", str(shadow)], check=True, capture_output=True)
-    assert (shadow / "libmldsa_keycheck.so").exists() and (shadow / "keycheck.res").exists()
-    assert _sha(build.LIB) == before, "building the key-check layer changed libmldsa_hip.so"
-    subprocess.run(["make", "-C", str(shadow), "clean"], check=True, capture_output=True)
-    assert not (shadow / "libmldsa_keycheck.so").exists() and not list(shadow.glob("*.res")) and not list(shadow.glob("*.o"))
-    mk = open(os.path.join(KC_DIR, "Makefile")).read()
-    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
-    mk += open(os.path.join(KC_DIR, "..", "layer", "layer.mk")).read()
-    assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
-    assert "-Rpass-analysis=kernel-resource-usage" in mk
-
-
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return set(re.findall(r"\b(mldsa_[a-z0-9_]+)\s*\(", text))
+    clean_build("keycheck", _keycheck_lib, ("Makefile", "keycheck.hip"),
+                (build.LIB, build.PH_LIB, build.KEYS_LIB, build.MU_LIB, build.SEED_LIB, build.KEYCHECK_LIB), tmp_path)
 
 
 def test_header_is_strict_c99_and_declares_exactly_the_exported_symbols(keycheck, tmp_path):
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    if cc is None:
-        cc = "/opt/rocm/llvm/bin/clang"
-    src = tmp_path / "h.c"
-    src.write_text('#include "mldsa_keycheck.h"\n'
-                   "int main(void) { unsigned char x[MLDSA_KEY_PK]; x[0] = MLDSA_KEY_S1_RANGE | MLDSA_KEY_S2_RANGE | MLDSA_KEY_T0 | MLDSA_KEY_TR;\n"
-                   "  return mldsa_keycheck_abi_version() == MLDSA_KEYCHECK_ABI_VERSION && MLDSA_KEYCHECK_RANGE != MLDSA_KEYCHECK_PAIR\n"
-                   "         && mldsa_keycheck_scratch_bytes(MLDSA_65, 1) > x[0] && MLDSA_KEYCHECK_MAX_KEYS > 1 ? 0 : 1; }\n")
-    subprocess.run([cc, "-std=c99", "-pedantic-errors", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
-                   check=True, capture_output=True)
-    out = subprocess.run(["nm", "-D", "--defined-only", _keycheck_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
-    exported = {n for n in exported if n.startswith("mldsa_")}
-    declared = _declared(_keycheck_lib.HEADER_PATH)
-    assert declared == exported, (sorted(declared - exported), sorted(exported - declared))
-    assert declared == set(_keycheck_lib._SIGNATURES) == EXPORTS
-    for name in declared:  # ctypes finds every one of them
-        assert getattr(keycheck, name) is not None
-    # the new names are not the core's
-    assert not declared & set(_lib.declared_symbols())
-    text = open(_keycheck_lib.HEADER_PATH).read()
-    assert '#include "mldsa_hip.h"' in text
+    declared, text = header_and_exports(
+        _keycheck_lib, keycheck,
+        "int main(void) { unsigned char x[MLDSA_KEY_PK]; x[0] = MLDSA_KEY_S1_RANGE | MLDSA_KEY_S2_RANGE | MLDSA_KEY_T0 | MLDSA_KEY_TR;\n"
+        "  return mldsa_keycheck_abi_version() == MLDSA_KEYCHECK_ABI_VERSION && MLDSA_KEYCHECK_RANGE != MLDSA_KEYCHECK_PAIR\n"
+        "         && mldsa_keycheck_scratch_bytes(MLDSA_65, 1) > x[0] && MLDSA_KEYCHECK_MAX_KEYS > 1 ? 0 : 1; }\n",
+        r"\b(mldsa_[a-z0-9_]+)\s*\(", tmp_path)
+    assert declared == EXPORTS
     assert "#define MLDSA_KEYCHECK_ABI_VERSION 1" in text and keycheck.mldsa_keycheck_abi_version() == _keycheck_lib.ABI_VERSION == 1
     assert "#define MLDSA_KEYCHECK_MAX_KEYS ((size_t)1 << 24)" in text and _keycheck_lib.MAX_KEYS == 1 << 24
     for name, value in (("MLDSA_KEY_S1_RANGE", 1), ("MLDSA_KEY_S2_RANGE", 2), ("MLDSA_KEY_T0", 4), ("MLDSA_KEY_TR", 8), ("MLDSA_KEY_PK", 16),
@@ -107,24 +51,12 @@ def test_header_is_strict_c99_and_declares_exactly_the_exported_symbols(keycheck
 
 
 def test_layered_on_the_one_core_library(keycheck):
-    dyn = subprocess.run(["readelf", "-d", _keycheck_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert re.search(r"NEEDED.*\[libmldsa_hip\.so\]", dyn)
-    assert re.search(r"(RUNPATH|RPATH).*\$ORIGIN/\.\./csrc", dyn)
-    mapped = set()
-    for ln in open("/proc/self/maps"):
-        if ln.rstrip().endswith("libmldsa_hip.so"):
-            mapped.add(os.stat(ln.split()[-1]).st_ino)
-    assert len(mapped) == 1, mapped  # two copies would be two HIP module registrations and a foreign mldsa_ctx
-    out = subprocess.run(["nm", "-D", _keycheck_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    undefined = {ln.split()[-1] for ln in out.splitlines() if " U " in ln}
-    defined = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    # the sampling, A s1 and the import itself are the core's; A s1 comes from the fused kernel, not from the three seams
-    for name in ("mldsa_expand_a", "mldsa_verify_arith", "mldsa_sk_expand", "mldsa_memset", "mldsa_get_params", "mldsa_ctx_device",
-                 "mldsa_last_error"):
-        assert name in undefined, name
-    for name in ("mldsa_ntt", "mldsa_mat_vec_mul", "mldsa_inv_ntt", "mldsa_keygen", "mldsa_bit_unpack", "mldsa_get_public_key"):
-        assert name not in undefined, name
-    assert not defined & set(_lib.declared_symbols())
+    layered_on_core(
+        _keycheck_lib.LIB_PATH,
+        # the sampling, A s1 and the import itself are the core's; A s1 comes from the fused kernel, not from the three seams
+        needs=("mldsa_expand_a", "mldsa_verify_arith", "mldsa_sk_expand", "mldsa_memset", "mldsa_get_params", "mldsa_ctx_device",
+               "mldsa_last_error"),
+        never=("mldsa_ntt", "mldsa_mat_vec_mul", "mldsa_inv_ntt", "mldsa_keygen", "mldsa_bit_unpack", "mldsa_get_public_key"))
 
 
 def _formula(pset, n):
@@ -133,37 +65,22 @@ def _formula(pset, n):
 
 
 def test_scratch_size_follows_the_documented_formula(keycheck):
-    fn = keycheck.mldsa_keycheck_scratch_bytes
-    for pset in KL:
-        last = 0
-        for n in (0, 1, 2, 63, 64, 65, 127, 128, 1000, 65536, 65537, 1 << 24):
-            got = fn(pset, n)
-            assert got == _formula(pset, n), (pset, n)
-            assert got >= last  # non-decreasing in n
-            last = got
-        for n in ((1 << 24) + 1, 2 ** 63, 2 ** 64 - 1):
-            assert fn(pset, n) == 0
-    for bad in (0, 43, 66, -1, 128):
-        assert fn(bad, 10) == 0
+    scratch_sweep(keycheck.mldsa_keycheck_scratch_bytes, _formula, 1 << 24)
     # the formula is the header's
     text = open(_keycheck_lib.HEADER_PATH).read()
     assert "n_keys (1024 (K L + L + 2 K + 1) + 320 K + 48) = n_keys * 31024 / 51120 / 84528" in text
     assert [_formula(s, 1) for s in (44, 65, 87)] == [31024, 51120, 84528]
-    for pset, (pk_len, sk_len) in PK_SK.items():
-        p = _lib.get_params(pset)
+    for pset, p in core_params().items():
         y = kc.Layout(pset)
-        assert (p.pk_len, p.sk_len, p.k, p.l, p.eta) == (pk_len, sk_len) + KL[pset] + (y.eta,)
-        assert (y.pk_len, y.sk_len) == (pk_len, sk_len)
+        assert (p.pk_len, p.sk_len, p.eta) == (y.pk_len, y.sk_len, y.eta)
         # what the layout and the 16-byte loads rely on: every section of a key and every part of the scratch starts on a multiple of 16
-        assert pk_len == 32 + 320 * p.k and sk_len % 16 == 0 and pk_len % 16 == 0 and _formula(pset, 1) % 16 == 0
+        assert _formula(pset, 1) % 16 == 0
         assert y.s1 % 16 == 0 and y.s2 % 16 == 0 and y.t0 % 16 == 0 and (32 * y.b) % 16 == 0
 
 
 def test_argument_errors_never_abort(keycheck):
     null = None
-    buf = (C.c_uint8 * 4096)()
-    p = C.c_void_p((C.addressof(buf) + 255) // 256 * 256)  # 256-byte aligned
-    odd = C.c_void_p(p.value + 8)
+    buf, p, odd = aligned_buffer()
     big = 1 << 50
     err = keycheck.mldsa_keycheck_last_error
 
@@ -219,45 +136,13 @@ def test_argument_errors_never_abort(keycheck):
 
 
 def test_kernels_do_not_spill_and_sources_are_clean(keycheck):
-    res = sorted(glob.glob(os.path.join(KC_DIR, "*.res")))
-    assert res, "no .res files under fips204_amd/keycheck"
-    kernels = []
-    for path in res:
-        text = open(path).read()
-        assert "warning" not in text, path
-        names = re.findall(r"Function Name: (\S+)", text)
-        spills = re.findall(r"VGPRs Spill: (\d+)", text)
-        sgpr_spills = re.findall(r"SGPRs Spill: (\d+)", text)
-        scratch = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)
-        assert len(names) == len(spills) == len(sgpr_spills) == len(scratch)
-        for nm, v, sg, sc in zip(names, spills, sgpr_spills, scratch):
-            assert int(v) == 0 and int(sg) == 0 and int(sc) == 0, (nm, v, sg, sc)
-        kernels += names
+    kernels = kernel_resources(KC_DIR)
     for stem in ("k_kc_range", "k_kc_s1", "k_kc_row", "k_kc_tr", "k_kc_merge", "k_kc_wipe"):
         assert any(stem in nm for nm in kernels), stem
     assert sum("k_kc_tr" in nm for nm in kernels) == 3     # one per parameter set (K = 4, 6, 8)
     assert sum("k_kc_range" in nm for nm in kernels) == 2  # 3-bit fields (ML-DSA-44 and 87) and 4-bit fields (ML-DSA-65)
-    checked = 0
-    for f in sorted(os.listdir(KC_DIR)) + ["../../include/mldsa_keycheck.h", "../_keycheck_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
-        path = os.path.normpath(os.path.join(KC_DIR, f))
-        if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
-            continue
-        t = open(path, errors="replace").read()
-        checked += 1
-        assert "getenv" not in t and "printf" not in t, f
-        # the guard words of tests/test_source_guards_cpu.py
-        assert "__HIP_PLATFORM_AMD__" not in t and "__CUDACC__" not in t and "import triton" not in t, f
-        assert "secure_getenv" not in t and "environ" not in re.sub(r"//[^\n]*", "", t), f
-        # plain C++ only: every store is an ordinary vector store the compiler emits
-        assert not re.search(r"\basm\b", t), f
-        assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 6
-    # the core's device headers are included, never copied
-    src = open(os.path.join(KC_DIR, "keycheck.hip")).read()
-    assert '#include "../layer/layer_dev.h"' in src  # through the layers' shared device header: both links of the chain
-    dev = open(os.path.join(KC_DIR, "..", "layer", "layer_dev.h")).read()
-    for h in ("../csrc/keccak.h", "../csrc/field.h", "../csrc/rounding.h"):
-        assert f'#include "{h}"' in dev
+    sources_clean(KC_DIR, ["../../include/mldsa_keycheck.h", "../_keycheck_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"])
+    src = includes_the_core_device_headers(KC_DIR, "keycheck.hip")
     # the range kernel has one loop, whose bound is the parameter set's, and leaves it by no other way; neither it nor the row kernel
     # asks the wave what its lanes found before the verdict byte
     rng_src = src[src.index("void k_kc_range"):src.index("// ---", src.index("void k_kc_range"))]

@@ -1,83 +1,39 @@
 """The key-deduplication library (include/mldsa_keys.h, fips204_amd/keys/libmldsa_keys.so) without a device: its C ABI, how it is
 linked against the core, its host-only entry points and its kernels' resources and sources."""
 import ctypes as C
-import glob
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from fips204_amd import _keys_lib, _lib
+from layer_checks import (KL, PK_SK, ROOT, aligned_buffer, built, header_and_exports, kernel_resources, layered_on_core,
+                          links_the_core_and_never_builds_it, sources_clean)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS_DIR = os.path.join(ROOT, "fips204_amd", "keys")
-PARAMS = {44: (1312, 4, 4), 65: (1952, 6, 5), 87: (2592, 8, 7)}  # set -> PK_LEN, K, L
 
 
 @pytest.fixture(scope="module")
 def keys():
-    if not os.path.exists(_keys_lib.LIB_PATH) or not glob.glob(os.path.join(KEYS_DIR, "*.res")):
-        from fips204_amd import build
-        build.build()
-    return _keys_lib.load()
-
-
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return set(re.findall(r"\b(mldsa_keys_[a-z0-9_]+|mldsa_verify_pk_dedup)\s*\(", text))
+    return built(_keys_lib, KEYS_DIR)
 
 
 def test_header_is_strict_c99_and_declares_exactly_the_exported_symbols(keys, tmp_path):
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    if cc is None:
-        cc = "/opt/rocm/llvm/bin/clang"
-    src = tmp_path / "h.c"
-    src.write_text('#include "mldsa_keys.h"\n'
-                   "int main(void) { mldsa_keys_info i; i.n_rows = 0; i.route = MLDSA_KEYS_ROUTE_CACHED;\n"
-                   "  return mldsa_keys_abi_version() == MLDSA_KEYS_ABI_VERSION && i.route ? 0 : 1; }\n")
-    subprocess.run([cc, "-std=c99", "-pedantic-errors", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
-                   check=True, capture_output=True)
-    out = subprocess.run(["nm", "-D", "--defined-only", _keys_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
-    exported = {n for n in exported if n.startswith("mldsa_")}
-    declared = _declared(_keys_lib.HEADER_PATH)
-    assert declared == exported, (sorted(declared - exported), sorted(exported - declared))
-    assert declared == set(_keys_lib._SIGNATURES)
-    # the new names are not the core's
-    assert not declared & set(_lib.declared_symbols())
-    # the header includes the core's, as mldsa_ph.h does, and the Python constants are the header's
-    text = open(_keys_lib.HEADER_PATH).read()
-    assert '#include "mldsa_hip.h"' in text
+    _, text = header_and_exports(
+        _keys_lib, keys,
+        "int main(void) { mldsa_keys_info i; i.n_rows = 0; i.route = MLDSA_KEYS_ROUTE_CACHED;\n"
+        "  return mldsa_keys_abi_version() == MLDSA_KEYS_ABI_VERSION && i.route ? 0 : 1; }\n",
+        r"\b(mldsa_keys_[a-z0-9_]+|mldsa_verify_pk_dedup)\s*\(", tmp_path)
+    # the Python constants are the header's
     assert re.search(r"#define MLDSA_KEYS_PROBE_MAX (\d+)", text).group(1) == str(_keys_lib.PROBE_MAX)
     assert "#define MLDSA_KEYS_MAX_KEYS ((size_t)1 << 30)" in text and _keys_lib.MAX_KEYS == 1 << 30
     assert "#define MLDSA_KEYS_MAX_CACHED ((size_t)1 << 24)" in text and _keys_lib.MAX_CACHED == 1 << 24
 
 
 def test_layered_on_the_one_core_library(keys):
-    dyn = subprocess.run(["readelf", "-d", _keys_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert re.search(r"NEEDED.*\[libmldsa_hip\.so\]", dyn)
-    assert re.search(r"(RUNPATH|RPATH).*\$ORIGIN/\.\./csrc", dyn)
-    mapped = set()
-    for ln in open("/proc/self/maps"):
-        if ln.rstrip().endswith("libmldsa_hip.so"):
-            mapped.add(os.stat(ln.split()[-1]).st_ino)
-    assert len(mapped) == 1, mapped  # two copies would be two HIP module registrations and a foreign mldsa_ctx
-    # no core object is linked in: every core entry point the library uses is an undefined symbol, and it defines none of them
-    out = subprocess.run(["nm", "-D", _keys_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    undefined = {ln.split()[-1] for ln in out.splitlines() if " U " in ln}
-    defined = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    for name in ("mldsa_verify_pk", "mldsa_verify_cached_a", "mldsa_pk_expand", "mldsa_expand_a", "mldsa_get_params", "mldsa_ctx_device",
-                 "mldsa_last_error"):
-        assert name in undefined, name
-    assert not defined & set(_lib.declared_symbols())
-    # the Makefile links the core and never builds it
-    mk = open(os.path.join(KEYS_DIR, "Makefile")).read()
-    assert "include ../layer/layer.mk" in mk  # the recipe is the layers' shared one: read with the Makefile
-    mk += open(os.path.join(KEYS_DIR, "..", "layer", "layer.mk")).read()
-    assert "-lmldsa_hip" in mk and "make -C ../csrc" not in mk.replace('build the core first (make -C ../csrc)', "")
-    assert "-Rpass-analysis=kernel-resource-usage" in mk
+    layered_on_core(_keys_lib.LIB_PATH, needs=("mldsa_verify_pk", "mldsa_verify_cached_a", "mldsa_pk_expand", "mldsa_expand_a", "mldsa_get_params",
+                                               "mldsa_ctx_device", "mldsa_last_error"))
+    links_the_core_and_never_builds_it(KEYS_DIR)
 
 
 def _dedup_formula(n):
@@ -93,14 +49,14 @@ def _r(x):
 
 
 def _verify_formula(pset, n, m):
-    pk_len, k, l = PARAMS[pset]
+    pk_len, (k, l) = PK_SK[pset][0], KL[pset]
     return (_r(_dedup_formula(n)) + 2 * _r(4 * n) + 256 + _r(m * pk_len) + _r(32 * m) + _r(64 * m) + _r(1024 * k * m)
             + _r(1024 * k * l * m))
 
 
 def test_scratch_sizes_follow_the_documented_formulas(keys):
     assert keys.mldsa_keys_abi_version() == _keys_lib.ABI_VERSION == 1
-    for pset in PARAMS:
+    for pset in KL:
         for n in (0, 1, 2, 31, 32, 33, 63, 64, 65, 1000, 1024, 1025, 4096, 65536, 65537, (1 << 20) + 1, 1 << 30):
             assert keys.mldsa_keys_dedup_scratch_bytes(pset, n) == _dedup_formula(n), (pset, n)
             for m in (0, 1, 7, 1024, 8192, min(n, 1 << 24)):
@@ -122,10 +78,7 @@ def test_scratch_sizes_follow_the_documented_formulas(keys):
 def test_argument_errors_never_abort(keys):
     null = None
     seed = bytes(range(16))
-    buf = (C.c_uint8 * 4096)()
-    base = C.addressof(buf)
-    p = C.c_void_p((base + 255) // 256 * 256)  # 256-byte aligned, 3840 bytes behind it
-    odd = C.c_void_p(p.value + 8)
+    buf, p, odd = aligned_buffer()
     big = 1 << 40
 
     def dedup(ctx=null, pset=65, pk=p, n=4, sd=seed, bits=64, row_of=p, table=p, rows=4, n_rows=p, scratch=p, sb=big, stream=null):
@@ -178,40 +131,12 @@ def test_argument_errors_never_abort(keys):
 
 
 def test_kernels_do_not_spill_and_sources_are_clean(keys):
-    res = sorted(glob.glob(os.path.join(KEYS_DIR, "*.res")))
-    assert res, "no .res files under fips204_amd/keys"
-    n = 0
-    for path in res:
-        text = open(path).read()
-        names = re.findall(r"Function Name: (\S+)", text)
-        spills = re.findall(r"VGPRs Spill: (\d+)", text)
-        sgpr_spills = re.findall(r"SGPRs Spill: (\d+)", text)
-        scratch = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)
-        lds = re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)
-        assert len(names) == len(spills) == len(sgpr_spills) == len(scratch) == len(lds)
-        for nm, v, sg, sc, ld in zip(names, spills, sgpr_spills, scratch, lds):
-            assert int(v) == 0 and int(sg) == 0 and int(sc) == 0, (nm, v, sg, sc)
-            assert int(ld) == 0, (nm, ld)  # registers and shuffles do everything here
-        n += len(names)
-    assert n >= 13  # claim, confirm, gather for three key lengths; count, offsets, rank; compose
+    # registers and shuffles do everything here: no LDS either
+    assert len(kernel_resources(KEYS_DIR, lds_zero=True)) >= 13  # claim, confirm, gather for three key lengths; count, offsets, rank; compose
     # scalar-memory stores, scalar atomics, scalar-cache write-back / discard (spelled in pieces so that this file holds none of them)
     sp = "s" + "_"
     words = [sp + w for w in ("st" + "ore", "buffer_" + "st" + "ore", "scratch_" + "st" + "ore", "ato" + "mic", "buffer_" + "ato" + "mic",
                               "dca" + "che_wb", "dca" + "che_discard")]
     scalar_mem = re.compile("|".join(re.escape(w) for w in words), re.I)
-    checked = 0
-    for f in sorted(os.listdir(KEYS_DIR)) + ["../../include/mldsa_keys.h", "../_keys_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]:
-        path = os.path.normpath(os.path.join(KEYS_DIR, f))
-        if not f.endswith((".hip", ".h", ".cpp", ".py")) and os.path.basename(f) != "Makefile":
-            continue
-        t = open(path, errors="replace").read()
-        checked += 1
+    for f, t in sources_clean(KEYS_DIR, ["../../include/mldsa_keys.h", "../_keys_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]):
         assert not scalar_mem.search(t), f
-        assert "getenv" not in t and "printf" not in t, f
-        # the guard words of tests/test_source_guards_cpu.py
-        assert "__HIP_PLATFORM_AMD__" not in t and "__CUDACC__" not in t and "import triton" not in t, f
-        assert "secure_getenv" not in t and "environ" not in re.sub(r"//[^\n]*", "", t), f
-        # plain C++ and the HIP atomic builtins only; no wave waits for another
-        assert not re.search(r"\basm\b", t), f
-        assert "__builtin_amdgcn_s_sleep" not in t, f
-    assert checked >= 6

@@ -3,19 +3,17 @@ SHA-512/224, SHA-512/256, SHA3-224/256/384/512, SHAKE256) without a device: code
 other code, the SHA-2 initial values in the device source, and the host pre-hash.  Everything expected here comes from the
 suite's own table (ph_fips_list_cases.py), hashlib and FIPS 180-4 arithmetic, not from the product's tables."""
 import ctypes as C
-import glob
 import hashlib
 import os
 import re
-import subprocess
 from math import isqrt
 
 import pytest
 
 import ph_fips_list_cases as cases
 from fips204_amd import _lib, _ph_lib
+from layer_checks import ROOT, built, exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PH_DIR = os.path.join(ROOT, "fips204_amd", "ph")
 
 # name -> (code, last OID byte, digest bytes, hashlib name, the member of its family among the reference's three: their code)
@@ -31,10 +29,7 @@ PARENT_SYMBOLS = {
 
 @pytest.fixture(scope="module")
 def ph():
-    if not os.path.exists(_ph_lib.LIB_PATH) or not glob.glob(os.path.join(PH_DIR, "*.res")):
-        from fips204_amd import build
-        build.build()
-    return _ph_lib.load()
+    return built(_ph_lib, PH_DIR)
 
 
 def _macros():
@@ -92,9 +87,7 @@ def test_every_other_code_is_still_unknown_through_every_entry_point(ph):
 
 
 def test_exported_symbols_are_the_parents(ph):
-    out = subprocess.run(["nm", "-D", "--defined-only", _ph_lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
-    assert {n for n in exported if n.startswith("mldsa_")} == PARENT_SYMBOLS == set(_ph_lib._SIGNATURES)
+    assert {n for n in exported(_ph_lib.LIB_PATH) if n.startswith("mldsa_")} == PARENT_SYMBOLS == set(_ph_lib._SIGNATURES)
 
 
 # ---- FIPS 180-4 in plain integers: SHA-512's compression function, then the initial values of §5.3.4-5.3.6
