@@ -1,4 +1,4 @@
-// The host scaffold of a library layered on the core's C ABI (keys/, mu/, seed/, keycheck/; ph/ takes DeviceScope alone): the error slot
+// The host scaffold of a library layered on the core's C ABI (keys/, mu/, seed/, keycheck/, mus/; ph/ takes DeviceScope alone): the error slot
 // behind the library's mldsa_*_last_error, the device scope of a call, the scratch-layout helpers, and the checks that open and the
 // clearing that closes an entry point.
 // Everything here has internal linkage (the unnamed namespace).  The layered libraries are loaded into one process: a thread_local or

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _seed_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -973,6 +973,158 @@ class MlDsa:
         return self._sign_host_call(
             lambda *a: _ph_lib.check(_ph_lib.load().mldsa_hash_sign_host(self._ph_host(staging_bytes), self.pset, code, *a)),
             "hash_sign_host", "HashML-DSA", sk_bytes, messages, rnd, ctxs, key_idx, out)
+
+
+    # ---- mu of messages in pieces or in host memory (include/mldsa_mus.h) ------------------------
+    def mu_stream(self, tr, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE):
+        """mldsa_mus_init: sponge states of n_ops messages that arrive in pieces, with tr and the ctx prefix of `mode` absorbed.
+        tr, ctx_buf / ctx_off, key_idx: device tensors as for mu_device.  Returns a MuStream: update(piece_buf, piece_off) any
+        number of times, then final() -> (mu, mu_flag) as mu_device gives them."""
+        return MuStream(self, tr, n_ops, ctx_buf, ctx_off, key_idx, mode)
+
+    def _mus_host(self, staging_bytes):
+        """the mldsa_mus_host of this staging size on this context (created on first use, kept)"""
+        hosts = self.__dict__.setdefault("_mus_hosts", {})
+        h = hosts.get(staging_bytes)
+        if h is None:
+            h = _MusHost(self.hp, staging_bytes)
+            hosts[staging_bytes] = h
+        return h.handle
+
+    def _upload(self, a):
+        """a host array on the device; the bytes go through a ctypes view, so a read-only array needs no writable copy"""
+        t = torch.empty(a.shape, dtype=torch.uint8, device=self.device)
+        if a.size:
+            _lib.check(self.lib.mldsa_memcpy_h2d(_ptr(t), _np_ptr(np.ascontiguousarray(a)), a.size, _stream(self.device)))
+            torch.cuda.synchronize(self.device)
+        return t
+
+    def mu_host(self, tr, messages, ctxs=None, key_idx=None, mode=MODE_PURE, staging_bytes=0):
+        """mldsa_mus_host_compute: (mu [n_ops, 64] uint8, mu_flag [n_ops] int32) on the device from RAW messages in HOST memory of
+        any total size; the bytes stream through two staging chunks of `staging_bytes` (0 = the library's default), so device
+        memory does not grow with the messages.  tr: uint8 CUDA tensor [n_keys, 64]; messages / ctxs: list of byte strings or a
+        (flat uint8 array, uint64 offsets[n + 1]) pair in host memory; key_idx: None, an array, or an int32 CUDA tensor.
+        Blocks: mu is complete on return."""
+        tr = tr.contiguous().view(-1, 64)
+        n_ops = len(messages) if not isinstance(messages, tuple) else len(messages[1]) - 1
+        mflat, moff = self._host_strings(messages, n_ops, "messages")
+        cflat = coff = None
+        if ctxs is not None:
+            cflat, coff = self._host_strings(ctxs, n_ops, "ctxs")
+        if not isinstance(key_idx, torch.Tensor):
+            key_idx = self._stage_key_idx(key_idx, tr.shape[0], n_ops)
+        mu = torch.zeros((max(n_ops, 1), _mus_lib.MU_LEN), dtype=torch.uint8, device=self.device)
+        flag = torch.zeros(max(n_ops, 1), dtype=torch.int32, device=self.device)
+        # the call runs on the object's own streams: tr and key_idx must be complete, mu and mu_flag free of pending work
+        torch.cuda.synchronize(self.device)
+        _mus_lib.check(_mus_lib.load().mldsa_mus_host_compute(
+            self._mus_host(staging_bytes), mode, _ptr(tr), tr.shape[0], _optr(key_idx), _np_ptr(mflat), _np_ptr(moff), _np_ptr(cflat),
+            _np_ptr(coff), _ptr(mu), _ptr(flag), n_ops))
+        return mu[:n_ops], flag[:n_ops]
+
+    def verify_host_streamed(self, pk_bytes, messages, sigs, ctxs=None, key_idx=None, out=None, staging_bytes=0):
+        """verify_host(mode=MODE_PURE) with the messages streamed: the keys are uploaded and expanded, mu_host hashes the raw
+        messages in bounded device memory, verify_mu_device verifies from mu, the verdicts come back.  Returns a bool array."""
+        pk = self._np_u8(pk_bytes, self.PK_LEN, "pk")
+        sg = self._np_u8(sigs, self.SIG_LEN, "sigs")
+        n_keys, n_ops = pk.size // self.PK_LEN, sg.size // self.SIG_LEN
+        kidx = _check_key_idx(key_idx, n_keys, n_ops)
+        ok_h = self._host_out(out, np.uint8, n_ops, "verify_host_streamed: out") if out is not None else np.zeros(max(n_ops, 1), dtype=np.uint8)
+        if n_ops == 0:
+            return ok_h[:0].astype(bool)
+        pks = self.public_keys_from_bytes(self._upload(pk.reshape(n_keys, self.PK_LEN)))
+        kidx_d = None if kidx is None else torch.as_tensor(kidx.view(np.int32)).to(self.device)
+        mu, flag = self.mu_host(pks.tr, messages, ctxs, kidx_d, MODE_PURE, staging_bytes)
+        ok = torch.zeros(n_ops, dtype=torch.uint8, device=self.device)
+        self.verify_mu_device(pks, mu, self._upload(sg.reshape(n_ops, self.SIG_LEN)), ok, n_ops, kidx_d, mu_flag=flag)
+        torch.cuda.synchronize(self.device)
+        ok_h[:n_ops] = ok.cpu().numpy()
+        return ok_h[:n_ops].astype(bool)
+
+    def sign_host_streamed(self, sk_bytes, messages, rnd, ctxs=None, key_idx=None, out=None, staging_bytes=0):
+        """sign_host(mode=MODE_PURE) with the messages streamed, as verify_host_streamed: mu_host, then sign_mu_device.  Returns
+        uint8 [n_ops, SIG_LEN]; out: (sig uint8[n_ops, SIG_LEN], status int32[n_ops]) buffers of the caller.  The expanded private
+        fields are zeroised before the call returns."""
+        sk = self._np_u8(sk_bytes, self.SK_LEN, "sk")
+        rn = self._np_u8(rnd, 32, "rnd")
+        n_keys, n_ops = sk.size // self.SK_LEN, rn.size // 32
+        kidx = _check_key_idx(key_idx, n_keys, n_ops)
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 2:
+                raise ValueError("sign_host_streamed: out = (sig uint8[n_ops, SIG_LEN], status int32[n_ops])")
+            sig_h = self._host_out(out[0], np.uint8, n_ops * self.SIG_LEN, "sign_host_streamed: out[0] (signatures)")
+            status_h = self._host_out(out[1], np.int32, n_ops, "sign_host_streamed: out[1] (status)")
+            sig_h = sig_h.reshape(-1)[:n_ops * self.SIG_LEN].reshape(n_ops, self.SIG_LEN) if n_ops else sig_h
+        else:
+            sig_h, status_h = np.zeros((max(n_ops, 1), self.SIG_LEN), dtype=np.uint8), np.zeros(max(n_ops, 1), dtype=np.int32)
+        if n_ops == 0:
+            return sig_h[:0]
+        sk_d = self._upload(sk.reshape(n_keys, self.SK_LEN))
+        sks = self.private_keys_from_bytes(sk_d)
+        try:
+            kidx_d = None if kidx is None else torch.as_tensor(kidx.view(np.int32)).to(self.device)
+            mu, flag = self.mu_host(sks.tr, messages, ctxs, kidx_d, MODE_PURE, staging_bytes)
+            sigs = torch.zeros((n_ops, self.SIG_LEN), dtype=torch.uint8, device=self.device)
+            status = torch.zeros(n_ops, dtype=torch.int32, device=self.device)
+            self.sign_mu_device(sks, mu, self._upload(rn.reshape(n_ops, 32)), sigs, n_ops, kidx_d, mu_flag=flag,
+                                status=status)
+            torch.cuda.synchronize(self.device)
+        finally:
+            sks.zeroize()
+            sk_d.zero_()
+        sig_h[:n_ops] = sigs.cpu().numpy()
+        status_h[:n_ops] = status.cpu().numpy()
+        if int(status_h[:n_ops].min()) < 0:
+            raise ValueError("ML-DSA.Sign: ctx too long")
+        return sig_h[:n_ops]
+
+
+class _MusHost:
+    """One mldsa_mus_host (staging chunks, streams, per-batch buffers) on a HotPath's context.  It keeps the HotPath alive;
+    destroying it does not need the context, so it may follow HotPath.close()."""
+
+    def __init__(self, hp, staging_bytes):
+        self.hp = hp
+        out = C.c_void_p(0)
+        _mus_lib.check(_mus_lib.load().mldsa_mus_host_create(hp._h, int(staging_bytes), C.byref(out)))
+        self.handle = out
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _mus_lib.load().mldsa_mus_host_destroy(self.handle)
+            self.handle = None
+        except Exception:
+            pass
+
+
+class MuStream:
+    """Sponge states of n_ops messages in device memory (mldsa_mus_init / _update / _final).  Every call is asynchronous on the
+    current stream; the states are used in stream order.  final() leaves the states as they are: more updates and another
+    final() give the mu of the longer messages."""
+
+    def __init__(self, m, tr, n_ops, ctx_buf=None, ctx_off=None, key_idx=None, mode=MODE_PURE):
+        self.m, self.n_ops = m, int(n_ops)
+        self.lib = _mus_lib.load()
+        tr = tr.contiguous().view(-1, 64)
+        self.state_bytes = self.lib.mldsa_mus_state_bytes(self.n_ops)
+        self.state = torch.empty(max(self.state_bytes, 8), dtype=torch.uint8, device=m.device)
+        _mus_lib.check(self.lib.mldsa_mus_init(m.hp._h, mode, _ptr(tr), tr.shape[0], _optr(key_idx), _optr(ctx_buf), _optr(ctx_off),
+                                               _ptr(self.state), self.state_bytes, self.n_ops, _stream(m.device)))
+
+    def update(self, piece_buf, piece_off):
+        """op i absorbs piece_buf[piece_off[i] : piece_off[i + 1]] (device tensors; piece_off: n_ops + 1 uint64 offsets)"""
+        _mus_lib.check(self.lib.mldsa_mus_update(self.m.hp._h, _ptr(self.state), self.state_bytes, _optr(piece_buf), _ptr(piece_off),
+                                                 self.n_ops, _stream(self.m.device)))
+        return self
+
+    def final(self):
+        """(mu [n_ops, 64] uint8, mu_flag [n_ops] int32): the shapes of mu_device"""
+        mu = torch.empty((max(self.n_ops, 1), _mus_lib.MU_LEN), dtype=torch.uint8, device=self.m.device)
+        flag = torch.empty(max(self.n_ops, 1), dtype=torch.int32, device=self.m.device)
+        _mus_lib.check(self.lib.mldsa_mus_final(self.m.hp._h, _ptr(self.state), self.state_bytes, _ptr(mu), _ptr(flag), self.n_ops,
+                                                _stream(self.m.device)))
+        return mu[:self.n_ops], flag[:self.n_ops]
 
 
 class _PhHost:
