@@ -92,7 +92,10 @@ class HotPath:
     def stats(self):
         st = _lib.Stats()
         _lib.check(self.lib.mldsa_get_stats(self._h, C.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in _lib.Stats._fields_}
+        out = {n: int(getattr(st, n)) for n, _ in _lib.Stats._fields_}
+        # the calls MlDsa.verify_device routed to libmldsa_vfy.so never reach the core's counters; that library launches every call directly
+        out["direct_calls"] += getattr(self, "_vfy_calls", 0)
+        return out
 
     def set_workspace(self, buf):
         """mldsa_ctx_set_workspace: a uint8 CUDA tensor of the caller's as the context's workspace (None: context-owned again).
@@ -116,14 +119,37 @@ class HotPath:
         _lib.check(self.lib.mldsa_reserve(self._h, pset, op, n_ops))
 
     # ---- per-stage timing (HIP events on the launch stream) -----------------------
+    # The large-batch verify library (libmldsa_vfy.so) records the stages of the calls MlDsa.verify_device routes to it, under the core's
+    # stage names.  Its record is switched on when the first such call is made while profiling is on (_vfy_profile_sync), not here: a host
+    # that profiles signing only never loads that library or makes it set up its streams.  The report is the sum of both records.
     def profile_enable(self, on=True):
         _lib.check(self.lib.mldsa_profile_enable(self._h, 1 if on else 0))
+        self._prof_on = bool(on)
+        if not on:
+            self._vfy_profile_sync(None)
+
+    def _vfy_profile_sync(self, vfy):
+        """brings the layer's record to the state profile_enable asked for; vfy: the loaded library, None = only if it is recording"""
+        want = getattr(self, "_prof_on", False)
+        if want == getattr(self, "_vfy_prof_on", False):
+            return
+        from . import _vfy_lib
+        _vfy_lib.check((vfy or _vfy_lib.load()).mldsa_vfy_profile_enable(self._h, 1 if want else 0))
+        self._vfy_prof_on = want
 
     def profile_report(self):
         import json
         buf = C.create_string_buffer(8192)
         _lib.check(self.lib.mldsa_profile_report(self._h, buf, len(buf)))
-        return json.loads(buf.value.decode())
+        stages = json.loads(buf.value.decode())
+        if getattr(self, "_vfy_prof_on", False):
+            from . import _vfy_lib
+            _vfy_lib.check(_vfy_lib.load().mldsa_vfy_profile_report(self._h, buf, len(buf)))
+            for name, st in json.loads(buf.value.decode()).items():
+                have = stages.setdefault(name, {"ms": 0.0, "calls": 0})
+                have["ms"] += st["ms"]
+                have["calls"] += st["calls"]
+        return stages
 
     # ---- src/ntt.rs ---------------------------------------------------------------
     def ntt(self, w, out=None):

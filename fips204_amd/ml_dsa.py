@@ -11,10 +11,17 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _seed_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _seed_lib, _vfy_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
+
+# verify_device calls of at least this many ops (per parameter set) that derive A_hat per op run on libmldsa_vfy.so
+# (include/mldsa_vfy.h).  Measured on the library as it ships, core and layer alternated four times per set and size over 8 192 ...
+# 65 536 ops (profiles/vfy_layer_ab.jsonl kind min_ops): the smallest size from which, at it and at every larger
+# size of the sweep, every run of the layer was faster than every run of the core.  Far above the core's single-launch limit
+# (MLDSA_OPT_SMALL_FUSED, 256 ops).
+VFY_MIN_OPS = {44: 24576, 65: 16384, 87: 65536}
 
 # Ph (src/types.rs:5-12) and hash_message (src/hashing.rs:316-354): the pre-hash of HashML-DSA is message-length-bound
 # host work; the device sees OID || PH(M) as the message of a MODE_PREHASH call.
@@ -314,9 +321,32 @@ class MlDsa:
         as `a_hat=` to verify_device / sign_device to skip the per-operation ExpandA."""
         return self.hp.expand_a(self.pset, keys.rho.contiguous())
 
+    def verify_route(self, n_ops, a_hat=None):
+        """the library a verify_device call of this shape runs on: "vfy" (libmldsa_vfy.so, the large-batch pass) from VFY_MIN_OPS[set]
+        ops on when A_hat is derived per op, else "core" """
+        return "vfy" if a_hat is None and VFY_MIN_OPS[self.pset] <= n_ops <= _vfy_lib.MAX_OPS else "core"
+
+    def _vfy_scratch(self, lib, n_ops):
+        """(pointer, bytes) of this object's scratch for the large-batch pass: one tensor, grown on demand, used in stream order"""
+        nb = lib.mldsa_vfy_scratch_bytes(self.pset, n_ops)
+        buf = getattr(self, "_vfy_buf", None)
+        if buf is None or buf.numel() < nb:
+            self._vfy_buf = buf = None  # (the old tensor goes back to the caching allocator before the larger one is asked for)
+            self._vfy_buf = buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        return _ptr(buf), buf.numel()
+
     def verify_device(self, pks, msg_buf, msg_off, sigs, ok, n_ops, ctx_buf=None, ctx_off=None, key_idx=None,
                       mode=MODE_PURE, a_hat=None):
         """Same, everything already resident in HBM (what bench.py times)."""
+        if self.verify_route(n_ops, a_hat) == "vfy":
+            lib = _vfy_lib.load()
+            self.hp._vfy_profile_sync(lib)
+            self.hp._vfy_calls = getattr(self.hp, "_vfy_calls", 0) + 1  # (HotPath.stats counts them as direct calls)
+            _vfy_lib.check(lib.mldsa_vfy_verify(
+                self.hp._h, self.pset, mode, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(key_idx),
+                _ptr(msg_buf), _ptr(msg_off), _optr(ctx_buf), _optr(ctx_off), _ptr(sigs), _ptr(ok), n_ops,
+                *self._vfy_scratch(lib, n_ops), _stream(self.device)))
+            return ok
         fn, first = (self.lib.mldsa_verify, pks.rho) if a_hat is None else (self.lib.mldsa_verify_cached_a, a_hat)
         _lib.check(fn(
             self.hp._h, self.pset, mode, _ptr(first), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(key_idx),
