@@ -1,10 +1,12 @@
 // libmldsa_vfy.so (include/mldsa_vfy.h): the large-batch, device-resident verify pass of the core's verify_batch (../csrc/pipeline.hip),
-// layered on the core's C ABI and rebuilt around two levers:
+// layered on the core's C ABI and rebuilt around three levers:
 //   - ExpandA on the folded Keccak round of keccak180.h (180 VALU per round instead of 190): the kernel is bound by its own instruction
 //     count, so fewer instructions are the only thing that moves it;
 //   - parts: the call is cut into parts (vfy_parts.h); ExpandA of part p + 1 runs on one library-owned stream while k_verify_main and
 //     the c~ hash of part p run on the other, and the front of every part (key-index check, mu, SampleInBall) on the caller's stream
 //     underneath.  Only stream events order the work.  The A_hat scratch is a ring of two parts.
+//   - k_verify_main's VALU stream: two rows a trip on two register sets, hint bits read from LDS, quad exchanges without a zeroed
+//     destination, w1Encode with one gather ("wave helpers of verify_main" below): the kernel is bound by instruction issue as well.
 // The device building blocks are the core's, included read-only (field.h, keccak.h, sampler_dev.h, ntt_wave.h, rounding.h, verify_dev.h,
 // challenge_dev.h); the kernels below are the core's kernels of the same names on those blocks, cut down to what this pass uses (packed
 // A_hat by op, c in bytes, lane-per-op hashes: the pass serves large calls only).  Formats and verdicts are the core's.
@@ -210,6 +212,133 @@ __global__ __launch_bounds__(64) void k_sample_in_ball(const uint8_t* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------- wave helpers of verify_main
+// k_verify_main is bound by instruction issue, so these are ../csrc/ntt_wave.h's transforms and ../csrc/rounding.h's w1Encode with the
+// same data movement in fewer VALU slots.  The core's quad exchanges are v_mov_b32_dpp with old = 0 and bound_ctrl off: the compiler has
+// to zero the destination first (one v_mov per exchange).  A quad permutation gives every lane a source, so `old` is never read: with
+// bound_ctrl on the zeroing goes, and where the consumer is a VOP2 (the v_or of w1Encode) the exchange folds into it.
+template <int CTRL>
+__device__ __forceinline__ int32_t dpp_all(int32_t v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
+
+// mldsa::swap_pair: the upper lane's x <-> the lower lane's y (lanes l, l ^ M)
+template <int M>
+__device__ __forceinline__ void swap_pair(int32_t& x, int32_t& y, int lane) {
+    if constexpr (M >= 4) {
+        mldsa::swap_pair<M>(x, y, lane);  // permlane swaps, and row DPP whose `old` is the value kept: nothing to zero
+    } else {
+        constexpr int CTRL = M == 2 ? 0x4E : 0xB1;  // quad_perm:[2,3,0,1] | [1,0,3,2]
+        const int32_t px = dpp_all<CTRL>(x), py = dpp_all<CTRL>(y);
+        const bool up = (lane & M) != 0;
+        x = up ? py : x;
+        y = up ? y : px;
+    }
+}
+template <int M>
+__device__ __forceinline__ void xchg_hi(int32_t r[4], int lane) {
+    swap_pair<M>(r[0], r[2], lane);
+    swap_pair<M>(r[1], r[3], lane);
+}
+template <int M>
+__device__ __forceinline__ void xchg_lo(int32_t r[4], int lane) {
+    swap_pair<M>(r[0], r[1], lane);
+    swap_pair<M>(r[2], r[3], lane);
+}
+
+// mldsa::ntt_fwd_wave / ntt_inv_wave on the exchanges above: the same butterflies in the same order, the same twiddle tables
+template <class TW>
+__device__ __forceinline__ void ntt_fwd_wave(int32_t r[4], const TW& tw, int lane) {
+    using mldsa::bf_ct;
+    bf_ct(r[0], r[2], mldsa::ZF1);
+    bf_ct(r[1], r[3], mldsa::ZF1);
+    bf_ct(r[0], r[1], mldsa::ZF2);
+    bf_ct(r[2], r[3], mldsa::ZF3);
+    xchg_hi<32>(r, lane);
+    bf_ct(r[0], r[2], tw.get(0));
+    bf_ct(r[1], r[3], tw.get(1));
+    xchg_lo<16>(r, lane);
+    bf_ct(r[0], r[1], tw.get(2));
+    bf_ct(r[2], r[3], tw.get(3));
+    xchg_hi<8>(r, lane);
+    bf_ct(r[0], r[2], tw.get(4));
+    bf_ct(r[1], r[3], tw.get(5));
+    xchg_lo<4>(r, lane);
+    bf_ct(r[0], r[1], tw.get(6));
+    bf_ct(r[2], r[3], tw.get(7));
+    xchg_hi<2>(r, lane);
+    bf_ct(r[0], r[2], tw.get(8));
+    bf_ct(r[1], r[3], tw.get(9));
+    xchg_lo<1>(r, lane);
+    bf_ct(r[0], r[1], tw.get(10));
+    bf_ct(r[2], r[3], tw.get(11));
+}
+template <class TW>
+__device__ __forceinline__ void ntt_inv_wave(int32_t r[4], const TW& tw, int lane, int32_t f) {
+    using mldsa::bf_gs;
+    bf_gs(r[0], r[1], tw.get(0));
+    bf_gs(r[2], r[3], tw.get(1));
+    bf_gs(r[0], r[2], tw.get(2));
+    bf_gs(r[1], r[3], tw.get(3));
+    xchg_lo<1>(r, lane);
+    bf_gs(r[0], r[1], tw.get(4));
+    bf_gs(r[2], r[3], tw.get(5));
+    xchg_hi<2>(r, lane);
+    bf_gs(r[0], r[2], tw.get(6));
+    bf_gs(r[1], r[3], tw.get(7));
+    xchg_lo<4>(r, lane);
+    bf_gs(r[0], r[1], tw.get(8));
+    bf_gs(r[2], r[3], tw.get(9));
+    xchg_hi<8>(r, lane);
+    bf_gs(r[0], r[2], tw.get(10));
+    bf_gs(r[1], r[3], tw.get(11));
+    xchg_lo<16>(r, lane);
+    bf_gs(r[0], r[1], tw.get(12));
+    bf_gs(r[2], r[3], tw.get(13));
+    xchg_hi<32>(r, lane);
+    const int32_t zf = (int32_t)((((int64_t)mldsa::ZI1 * f) % mldsa::Q) * mldsa::RINV_MOD_Q % mldsa::Q);  // ZI1 * f * 2^-32 mod q
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int32_t a = r[k], b = r[k + 2];
+        r[k] = mldsa::caddq(mldsa::mont_mul(a + b, f));
+        r[k + 2] = mldsa::caddq(mldsa::mont_mul(a - b, zf));
+    }
+}
+
+// mldsa::pack_w1_strided: v[k] = the field of coefficient 64 k + lane, the same bytes at dst.
+template <bool G2HI>
+__device__ __forceinline__ void pack_w1_strided(const uint32_t v[4], uint8_t* dst, int lane) {
+    if constexpr (G2HI) {
+        // 8 adjacent lanes make one dword of register k (8 nibbles).  OR over the quad for all four registers; then lane 8 m + k
+        // (k < 4) picks ITS register's quad sum and takes the other quad's from lane + 4, which picked the same register: one
+        // exchange where the core mirrors all four registers across the half row and selects afterwards (by branches, as compiled).
+        uint32_t d[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = v[k] << (4 * (lane & 7));
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] |= (uint32_t)dpp_all<0xB1>((int32_t)d[k]);  // quad_perm:[1,0,3,2]
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] |= (uint32_t)dpp_all<0x4E>((int32_t)d[k]);  // quad_perm:[2,3,0,1]
+        const uint32_t d01 = (lane & 1) ? d[1] : d[0], d23 = (lane & 1) ? d[3] : d[2];
+        uint32_t mine = (lane & 2) ? d23 : d01;
+        mine |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)mine, 0x104, 0xF, 0xF, true);  // row_shl:4: lane i reads lane i + 4
+        if (!(lane & 4)) mldsa::store_row(reinterpret_cast<uint32_t*>(dst) + 8 * (lane & 3) + (lane >> 3), mine);
+    } else {
+        // coefficient quads sit in adjacent lanes: 4 x 6 bits = 3 bytes, assembled with DPP quad permutes
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t n1 = (uint32_t)dpp_all<0xB1>((int32_t)v[k]);      // lane ^ 1
+            const uint32_t pair = (lane & 1) ? 0u : (v[k] | (n1 << 6));      // 12 bits in even lanes
+            const uint32_t n2 = (uint32_t)dpp_all<0x4E>((int32_t)pair);      // lane ^ 2
+            if (!(lane & 3)) {
+                const uint32_t q24 = pair | (n2 << 12);
+                uint8_t* d = dst + 48 * k + 3 * (lane >> 2);
+                d[0] = (uint8_t)q24; d[1] = (uint8_t)(q24 >> 8); d[2] = (uint8_t)(q24 >> 16);
+            }
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------------------------- verify_main
 // The core's k_verify_main<.., APACK = true> with A_hat by op: one wave per op, sigDecode, NTT(z), NTT(c), the K rows of
 // A_hat o z_hat - c_hat o t1_hat -> inverse NTT -> UseHint -> w1Encode, the next A_hat row in flight under the current row's inverse NTT.
@@ -271,10 +400,10 @@ __global__ __launch_bounds__(64 * VW) __attribute__((amdgpu_waves_per_eu(MINW)))
                 const uint32_t d = mldsa::load_once<mldsa::NT_ZC>(c + op * 64 + ul);
                 r[0] = (int8_t)(d & 0xFF); r[1] = (int8_t)((d >> 8) & 0xFF); r[2] = (int8_t)((d >> 16) & 0xFF); r[3] = (int8_t)(d >> 24);
             }
-            mldsa::ntt_fwd_wave(r, ftw, lane);
+            mldsa_vfy::ntt_fwd_wave(r, ftw, lane);
             if (j == L) {
 #pragma unroll
-                for (int k = 0; k < 4; k++) r[k] = mldsa::mont_mul(r[k], 1);  // c_hat * 2^-32
+                for (int k = 0; k < 4; k++) r[k] = mldsa::mont_mul(r[k], -1);  // -c_hat * 2^-32: the rows ADD its product with t1
             }
             zh[wave][j][lane] = make_int4(r[0], r[1], r[2], r[3]);
         }
@@ -284,49 +413,53 @@ __global__ __launch_bounds__(64 * VW) __attribute__((amdgpu_waves_per_eu(MINW)))
             znorm[op] = __ballot(zbad) != 0ull ? 0x7fffffff : 0;
             hvalid[op] = hint_ok ? 1 : 0;
         }
-        // ---- rows
-#pragma unroll 1
-        for (int i = 0; i < K; i++) {
-            asm volatile("" ::: "memory");
+        // ---- rows, two per trip on two named register sets (K is even): the prefetch of row i + 1 lands in the registers that row reads,
+        // where one set cost 15 v_mov a row to hand `next` over to `current`
+        auto row = [&](int i, const Packed3 (&a_cur)[L], const int4& t_cur, Packed3 (&a_nxt)[L], int4& t_nxt, bool more) {
             // 64-bit accumulation, one Montgomery reduction per coefficient and row (field.h): |a| < 2^24, |z_hat| < 9 q, at most
-            // L + 1 <= 8 terms: |sum| < 2^54 = the reduction's input bound
-            int64_t acc64[4] = {0, 0, 0, 0};
+            // L + 1 <= 8 terms: |sum| < 2^54 = the reduction's input bound.  c_hat * 2^-32 in (-q, q); t1 from mldsa_pk_expand is in
+            // (-q, q); zh[L] holds it negated, so the whole row is one chain of v_mad_i64_i32 with no 64-bit subtraction behind it.
+            const int4 cv = zh[wave][L][lane];
+            int64_t acc64[4] = {(int64_t)cv.x * t_cur.x, (int64_t)cv.y * t_cur.y, (int64_t)cv.z * t_cur.z, (int64_t)cv.w * t_cur.w};
 #pragma unroll
             for (int j = 0; j < L; j++) {
                 const int4 zv = zh[wave][j][lane];
-                const int4 a4 = mldsa::unpack24(av[j]);
+                const int4 a4 = mldsa::unpack24(a_cur[j]);
                 acc64[0] += (int64_t)a4.x * zv.x;
                 acc64[1] += (int64_t)a4.y * zv.y;
                 acc64[2] += (int64_t)a4.z * zv.z;
                 acc64[3] += (int64_t)a4.w * zv.w;
             }
-            const int4 cv = zh[wave][L][lane];  // c_hat * 2^-32 in (-q, q); t1 from mldsa_pk_expand is in (-q, q)
-            acc64[0] -= (int64_t)cv.x * tv.x;
-            acc64[1] -= (int64_t)cv.y * tv.y;
-            acc64[2] -= (int64_t)cv.z * tv.z;
-            acc64[3] -= (int64_t)cv.w * tv.w;
             int32_t acc[4];
-            if (i + 1 < K) {  // next row: in flight during this row's inverse transform
+            if (more) {  // next row: in flight during this row's inverse transform
 #pragma unroll
-                for (int j = 0; j < L; j++) av[j] = mldsa::load_row<mldsa::NT_A_VERIFY>(&arow[(unsigned)(((i + 1) * L + j) * 64) + ul]);
-                tv = trow[(unsigned)((i + 1) * 64) + ul];
+                for (int j = 0; j < L; j++) a_nxt[j] = mldsa::load_row<mldsa::NT_A_VERIFY>(&arow[(unsigned)(((i + 1) * L + j) * 64) + ul]);
+                t_nxt = trow[(unsigned)((i + 1) * 64) + ul];
             }
-            // hint bits of coefficients 64 k + lane: mask word 2 k + (lane >> 5); one dword per lane, handed out with v_readlane
-            const uint32_t hword = hint_lds[wave][24 + i * 8 + (ul & 7)];
 #pragma unroll
             for (int k = 0; k < 4; k++) acc[k] = mldsa::mont_reduce64(acc64[k]);  // (-q, q): the inverse transform's input range
-            mldsa::ntt_inv_wave(acc, itw, lane, mldsa::F_MONT2);
-            // acc[k] = w'[64 k + lane], canonical.  UseHint, then pack BITS-bit fields.
+            mldsa_vfy::ntt_inv_wave(acc, itw, lane, mldsa::F_MONT2);
+            // acc[k] = w'[64 k + lane], canonical.  UseHint, then pack BITS-bit fields.  The hint bit of coefficient 64 k + lane is bit
+            // lane & 31 of mask word 2 k + (lane >> 5): read from the masks hint_unpack_wave left in LDS, two addresses per wave and k
+            const uint32_t* hrow = hint_lds[wave] + 24 + i * 8 + (ul >> 5);
             uint8_t* dst = w1 + op * w1_stride + (size_t)i * (32 * BITS);
             uint32_t v[4];
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane((int)hword, 2 * k), whi = (uint32_t)__builtin_amdgcn_readlane((int)hword, 2 * k + 1);
-                const uint32_t hwk = lane < 32 ? wlo : whi;
-                const uint32_t h = (hwk >> (lane & 31)) & 1u;
+                const uint32_t h = (hrow[2 * k] >> (ul & 31)) & 1u;
                 v[k] = (uint32_t)mldsa::use_hint<G2HI>((int32_t)h, acc[k]);
             }
-            mldsa::pack_w1_strided<G2HI>(v, dst, lane);
+            pack_w1_strided<G2HI>(v, dst, lane);
+        };
+        static_assert(K % 2 == 0, "the row loop runs two rows a trip");
+        Packed3 aw[L];
+        int4 tw2;
+#pragma unroll 1
+        for (int i = 0; i < K; i += 2) {
+            asm volatile("" ::: "memory");
+            row(i, av, tv, aw, tw2, true);
+            asm volatile("" ::: "memory");
+            row(i + 1, aw, tw2, av, tv, i + 2 < K);
         }
     }
 }
