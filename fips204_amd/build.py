@@ -3,8 +3,8 @@ core and never rebuild it: the pre-hash library fips204_amd/ph/libmldsa_ph.so (i
 library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h), the external-mu library fips204_amd/mu/libmldsa_mu.so
 (include/mldsa_mu.h), the seed-form key library fips204_amd/seed/libmldsa_seed.so (include/mldsa_seed.h), the strict private-key
 import library fips204_amd/keycheck/libmldsa_keycheck.so (include/mldsa_keycheck.h), the mu-stream library
-fips204_amd/mus/libmldsa_mus.so (include/mldsa_mus.h) and the large-batch verify library fips204_amd/vfy/libmldsa_vfy.so
-(include/mldsa_vfy.h)."""
+fips204_amd/mus/libmldsa_mus.so (include/mldsa_mus.h), the wire-record library fips204_amd/rec/libmldsa_rec.so (include/mldsa_rec.h)
+and the large-batch verify library fips204_amd/vfy/libmldsa_vfy.so (include/mldsa_vfy.h)."""
 import os
 import subprocess
 
@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libmldsa_hip.so")
 # the layered libraries in build order: directory under fips204_amd/ -> library file name
 LAYERS = {"ph": "libmldsa_ph.so", "keys": "libmldsa_keys.so", "mu": "libmldsa_mu.so", "seed": "libmldsa_seed.so",
-          "keycheck": "libmldsa_keycheck.so", "mus": "libmldsa_mus.so", "vfy": "libmldsa_vfy.so"}
+          "keycheck": "libmldsa_keycheck.so", "mus": "libmldsa_mus.so", "rec": "libmldsa_rec.so", "vfy": "libmldsa_vfy.so"}
 # PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB
 for _name, _file in LAYERS.items():
     globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _seed_lib, _vfy_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _seed_lib, _vfy_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -1392,3 +1392,143 @@ class MlDsaBatcher:
         st = _lib.BatcherStats()
         _lib.check(self.lib.mldsa_batcher_get_stats(self._b, C.byref(st)))
         return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+
+# ---- verification from wire records (include/mldsa_rec.h) --------------------------------------------------------------------------
+def records_blob(records, pad=0, front=0, fill=0xC3):
+    """Lays records (pset, pk, message, sig, ctx) out in one buffer, field after field -- key, signature, message, context --, and
+    describes them: (blob, ops) = (uint8 numpy array, numpy array of _rec_lib.OP_DTYPE, one mldsa_rec_op per record).
+    pad: the gap in front of every field, one int or a sequence that is cycled through, so that a caller chooses every field's
+    alignment; front: bytes in front of the first gap; the gaps hold `fill`."""
+    pads = [int(pad)] if np.isscalar(pad) else [int(x) for x in pad]
+    ops = np.zeros(len(records), dtype=_rec_lib.OP_DTYPE)
+    parts, at, k = [bytes([fill]) * front], front, 0
+    for i, (pset, pk, message, sig, ctx) in enumerate(records):
+        if len(ctx) > 0xFFFF or len(message) > 0xFFFFFFFF:
+            raise ValueError("records_blob: a context or message too long for its descriptor field")
+        ops[i]["set"], ops[i]["msg_len"], ops[i]["ctx_len"] = pset, len(message), len(ctx)
+        for name, field in (("pk_off", pk), ("sig_off", sig), ("msg_off", message), ("ctx_off", ctx)):
+            gap = pads[k % len(pads)]
+            k += 1
+            parts += [bytes([fill]) * gap, bytes(field)]
+            ops[i][name] = at + gap
+            at += gap + len(field)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), ops
+
+
+class MlDsaRecords:
+    """Batched verification straight from serialized records on one GPU, any mix of parameter sets in one call: libmldsa_rec.so
+    (include/mldsa_rec.h).  blob = uint8 CUDA tensor (any alignment: a slice will do), ops = uint8 CUDA tensor holding n_ops
+    mldsa_rec_op descriptors (ops_tensor() uploads a numpy array of _rec_lib.OP_DTYPE)."""
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.rec = _rec_lib.load()
+        self._sets = {}
+
+    def set(self, pset):
+        """the MlDsa of one parameter set on this object's context"""
+        if pset not in self._sets:
+            self._sets[pset] = MlDsa(pset, hotpath=self.hp)
+        return self._sets[pset]
+
+    def ops_tensor(self, ops):
+        a = np.ascontiguousarray(ops, dtype=_rec_lib.OP_DTYPE)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(40, np.uint8)).to(self.device)
+
+    @staticmethod
+    def _n_ops(ops, n_ops):
+        if ops.dtype != torch.uint8 or ops.numel() % 40:
+            raise ValueError("ops: a uint8 tensor of n_ops * 40 bytes expected")
+        return ops.numel() // 40 if n_ops is None else int(n_ops)
+
+    def plan_device(self, blob, ops, n_ops=None):
+        """mldsa_rec_plan, asynchronous on the current stream: (class_slot int32 [n_ops] -- (class << 30) | slot, to be read as
+        uint32 --, totals int64 [10] -- ops per class 44 / 65 / 87 / refused, message bytes per class, context bytes per class --,
+        plan uint8: the working memory pack_device takes)."""
+        n = self._n_ops(ops, n_ops)
+        class_slot = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        totals = torch.zeros(10, dtype=torch.int64, device=self.device)
+        plan = torch.empty(max(self.rec.mldsa_rec_plan_bytes(n), 256), dtype=torch.uint8, device=self.device)
+        _rec_lib.check(self.rec.mldsa_rec_plan(self.hp._h, _ptr(blob), blob.numel(), _ptr(ops), n, _ptr(class_slot), _ptr(totals), _ptr(plan),
+                                               plan.numel(), _stream(self.device)))
+        return class_slot[:n], totals, plan
+
+    def pack_device(self, blob, ops, class_slot, totals, plan, n_ops=None, arena=None):
+        """mldsa_rec_pack behind plan_device: waits for the current stream to read the totals (unless `totals` is already a
+        _rec_lib.RecTotals), then packs asynchronously.  Returns {pset: dict(n, pk [n, PK_LEN], sigs [n, SIG_LEN], msgs, msg_off
+        [n + 1], ctxs, ctx_off [n + 1], ok [n])}, every tensor a view of one arena -- what verify_pk_device, verify_pk_dedup_device
+        or hash_verify_pk_device of MlDsa(pset) take."""
+        n = self._n_ops(ops, n_ops)
+        if not isinstance(totals, _rec_lib.RecTotals):
+            torch.cuda.current_stream(self.device).synchronize()
+            h = [int(x) for x in totals.cpu().tolist()]
+            totals = _rec_lib.RecTotals()
+            totals.n[:], totals.msg_bytes[:], totals.ctx_bytes[:] = h[0:4], h[4:7], h[7:10]
+        need = self.rec.mldsa_rec_scratch_bytes(totals.n[0], totals.n[1], totals.n[2], sum(totals.msg_bytes), sum(totals.ctx_bytes))
+        if arena is None:
+            arena = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        out = _rec_lib.RecPacked()
+        _rec_lib.check(self.rec.mldsa_rec_pack(self.hp._h, _ptr(blob), blob.numel(), _ptr(ops), n, _ptr(class_slot), _ptr(plan), plan.numel(),
+                                               C.byref(totals), _ptr(arena), arena.numel(), C.byref(out), _stream(self.device)))
+        base, packed = arena.data_ptr(), {}
+        for c, pset in enumerate(_rec_lib.CLASS_SETS):
+            k, m = out.c[c], self.set(pset)
+            cut = lambda p, nbytes: arena[(p or base) - base:(p or base) - base + nbytes]  # noqa: E731
+            packed[pset] = dict(
+                n=int(k.n), pk=cut(k.pk, k.n * m.PK_LEN).view(int(k.n), m.PK_LEN), sigs=cut(k.sigs, k.n * m.SIG_LEN).view(int(k.n), m.SIG_LEN),
+                msgs=cut(k.msgs, max(int(totals.msg_bytes[c]), 1)), msg_off=cut(k.msg_off, 8 * (k.n + 1)).view(torch.int64),
+                ctxs=cut(k.ctxs, max(int(totals.ctx_bytes[c]), 1)), ctx_off=cut(k.ctx_off, 8 * (k.n + 1)).view(torch.int64), ok=cut(k.ok, k.n))
+        return packed
+
+    def verify_scratch(self, n_ops, msg_bytes, ctx_bytes):
+        """device scratch that no verify_device call of up to n_ops ops with these byte totals can outgrow, whatever its mix"""
+        nb = self.rec.mldsa_rec_front_bytes(n_ops) + self.rec.mldsa_rec_scratch_bytes_max(n_ops, msg_bytes, ctx_bytes)
+        return torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+
+    def verify_device(self, blob, ops, ok, n_ops=None, mode=MODE_PURE, scratch=None, info=None):
+        """mldsa_rec_verify: ok[i] = mldsa_verify_pk's verdict on record i under its own parameter set, 0 for a refused record.
+        Waits once for the current stream (the mix decides the layout).  scratch: a uint8 tensor, e.g. from verify_scratch(); None:
+        one that holds any mix whose messages and contexts fit the blob four times over (a call that needs more raises MldsaError
+        with MLDSA_ERR_NOMEM, and info names the need).  info: a dict that receives n44, n65, n87, refused, msg_bytes, ctx_bytes and
+        scratch_needed."""
+        n = self._n_ops(ops, n_ops)
+        if scratch is None:
+            scratch = self.verify_scratch(n, 4 * blob.numel(), 4 * blob.numel())
+        out = _rec_lib.RecInfo()
+        rc = self.rec.mldsa_rec_verify(self.hp._h, mode, _ptr(blob), blob.numel(), _ptr(ops), n, _ptr(ok), _ptr(scratch), scratch.numel(),
+                                       C.byref(out), _stream(self.device))
+        if info is not None and rc in (_lib.OK, _lib.ERR_NOMEM) and n:
+            info.update(n44=int(out.n[0]), n65=int(out.n[1]), n87=int(out.n[2]), refused=int(out.n[3]), msg_bytes=int(out.msg_bytes),
+                        ctx_bytes=int(out.ctx_bytes), scratch_needed=int(out.scratch_needed))
+        _rec_lib.check(rc)
+        return ok
+
+    def verify(self, records, mode=MODE_PURE, dedup=False, pad=0):
+        """A host list of (pset, pk, message, sig, ctx) -> a bool array, one verdict per record: the records are laid out in one
+        blob (records_blob) and verified from it.  dedup=True: the blob is planned and packed, and each parameter set's arrays run
+        through MlDsa(pset).verify_pk_dedup_device (equal keys are expanded once); same verdicts."""
+        n = len(records)
+        if n == 0:
+            return np.zeros(0, dtype=bool)
+        blob_h, ops_h = records_blob(records, pad=pad)
+        blob = torch.from_numpy(blob_h.copy() if blob_h.size else np.zeros(1, np.uint8)).to(self.device)[:blob_h.size]
+        ops = self.ops_tensor(ops_h)
+        ok = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        if not dedup:
+            self.verify_device(blob, ops, ok, n, mode)
+        else:
+            class_slot, totals, plan = self.plan_device(blob, ops, n)
+            packed = self.pack_device(blob, ops, class_slot, totals, plan, n)
+            cs = class_slot.cpu().numpy().view(np.uint32)
+            for c, pset in enumerate(_rec_lib.CLASS_SETS):
+                k = packed[pset]
+                if k["n"] == 0:
+                    continue
+                self.set(pset).verify_pk_dedup_device(k["pk"], k["msgs"], k["msg_off"], k["sigs"], k["ok"], k["n"], k["ctxs"], k["ctx_off"],
+                                                      None, mode)
+                mine = np.nonzero(cs >> 30 == c)[0]
+                ok[torch.from_numpy(mine).to(self.device)] = k["ok"][torch.from_numpy((cs[mine] & 0x3FFFFFFF).astype(np.int64)).to(self.device)]
+        torch.cuda.synchronize(self.device)
+        return ok.cpu().numpy().astype(bool)
