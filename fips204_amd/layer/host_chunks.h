@@ -1,14 +1,14 @@
-// The chunk plan of mldsa_mus_host_compute as pure host code (no HIP here: tests/cpp/mus_chunks_main.cpp compiles it alone, under the
-// sanitizers).  The bytes [off[0], off[n_ops]) of a batch of messages are cut into chunks of at most `staging` bytes at arbitrary byte
-// positions; a message may span any number of chunks and a chunk may hold any number of messages.  For every chunk the plan gives the
-// byte range, the range of ops that have bytes in it, and -- piece_lo / piece_hi, the two functions the update kernels apply to the one
-// offset table of the call -- where each of those ops' bytes lie in the chunk.
+// The chunk plan of the host-memory feed (host_feed.h: mldsa_hash_*_host, mldsa_mus_host_compute) as pure host code (no HIP here:
+// tests/cpp/host_chunks_main.cpp compiles it alone, under the sanitizers).  The bytes [off[0], off[n_ops]) of a batch of messages are cut
+// into chunks of at most `staging` bytes at arbitrary byte positions; a message may span any number of chunks and a chunk may hold any
+// number of messages.  For every chunk the plan gives the byte range, the range of ops that have bytes in it, and -- piece_lo / piece_hi,
+// the two functions mus's update kernels apply to the one offset table of the call -- where each of those ops' bytes lie in the chunk.
 // `off` is a table that mldsa_check_offsets has accepted: n_ops + 1 non-decreasing offsets.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-namespace mldsa_mus {
+namespace mldsa_layer {
 
 // The bytes of the pair [p0, p1) that fall into the window [win_lo, win_hi) are [piece_lo(p0, win_lo), piece_hi(p1, win_hi)), if that
 // is not empty.  (constexpr: the kernels call the same two functions.)
@@ -55,4 +55,4 @@ private:
     size_t first_ = 0;
 };
 
-}  // namespace mldsa_mus
+}  // namespace mldsa_layer

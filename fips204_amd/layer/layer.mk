@@ -1,5 +1,7 @@
 # The build recipe of a library layered on libmldsa_hip.so, included by the Makefiles of ../ph, ../keys, ../mu, ../seed, ../keycheck and ../mus
 # (paths are relative to those directories).  The including Makefile sets LIB (the library's file name), OBJS and HDRS.
+# The headers of this directory go into HDRS as each library includes them: layer_host.h and layer_dev.h, and for ../ph and ../mus
+# host_feed.h with host_chunks.h.
 # The core library is built by ../csrc/Makefile and only linked here: nothing in this file rebuilds, relinks or re-flags it.
 # Every kernel's register / scratch / LDS use is written next to its object as <file>.res (-Rpass-analysis=kernel-resource-usage).
 HIPCC   ?= /opt/rocm/bin/hipcc

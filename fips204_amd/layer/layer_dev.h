@@ -1,5 +1,6 @@
-// The device helpers the layered libraries' kernels share (mu/, seed/, keycheck/): the wave-wide OR, the canonical representative, and
-// the shapes two or more of them agree on -- the LDS tile of the lane-per-state SHAKE256 and the packed t1 row.  Helpers only: every
+// The device helpers the layered libraries' kernels share (mu/, seed/, keycheck/; ph/stream.hip and mus/ take wave_max): the wave-wide OR
+// and maximum, the canonical representative, and the shapes two or more of them agree on -- the LDS tile of the lane-per-state SHAKE256
+// and the packed t1 row.  Helpers only: every
 // kernel (__global__) stays in its library's .hip file.  The core's device headers are included read-only.
 //
 // A piece is shared here only if every kernel that uses it compiles to the same instructions as with the piece written out.  Three did
@@ -34,6 +35,16 @@ constexpr int T1_ROW_DW = 80;  // a row of t1 in a wire public key: 256 coeffici
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+
+// maximum over the wave, the same value in every lane
+__device__ __forceinline__ size_t wave_max(size_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const size_t o = (size_t)__shfl_xor((unsigned long long)v, m);
+        v = o > v ? o : v;
+    }
     return v;
 }
 

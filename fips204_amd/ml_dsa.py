@@ -979,14 +979,16 @@ class MlDsa:
         update(piece_buf, piece_off) any number of times, then final() -> (rows, bad) as prehash_device gives them."""
         return PrehashStream(self, n_ops, ph)
 
-    def _ph_host(self, staging_bytes):
-        """the mldsa_ph_host of this staging size on this context (created on first use, kept)"""
-        hosts = self.__dict__.setdefault("_ph_hosts", {})
-        h = hosts.get(staging_bytes)
+    def _host_feed(self, loader, layer, staging_bytes):
+        """the mldsa_<layer>_host of this staging size on this context (created on first use, kept)"""
+        hosts = self.__dict__.setdefault("_host_feeds", {})
+        h = hosts.get((layer, staging_bytes))
         if h is None:
-            h = _PhHost(self.hp, staging_bytes)
-            hosts[staging_bytes] = h
+            h = hosts[(layer, staging_bytes)] = _HostFeed(self.hp, staging_bytes, loader, f"mldsa_{layer}_host_create", f"mldsa_{layer}_host_destroy")
         return h.handle
+
+    def _ph_host(self, staging_bytes):
+        return self._host_feed(_ph_lib, "ph", staging_bytes)
 
     def hash_verify_host(self, pk_bytes, messages, sigs, ctxs=None, ph=PH_SHA512, key_idx=None, out=None, staging_bytes=0):
         """mldsa_hash_verify_host: verify_host's arguments on RAW messages in host memory; the pre-hash `ph` is computed on the
@@ -1013,13 +1015,7 @@ class MlDsa:
         return MuStream(self, tr, n_ops, ctx_buf, ctx_off, key_idx, mode)
 
     def _mus_host(self, staging_bytes):
-        """the mldsa_mus_host of this staging size on this context (created on first use, kept)"""
-        hosts = self.__dict__.setdefault("_mus_hosts", {})
-        h = hosts.get(staging_bytes)
-        if h is None:
-            h = _MusHost(self.hp, staging_bytes)
-            hosts[staging_bytes] = h
-        return h.handle
+        return self._host_feed(_mus_lib, "mus", staging_bytes)
 
     def _upload(self, a):
         """a host array on the device; the bytes go through a ctypes view, so a read-only array needs no writable copy"""
@@ -1109,20 +1105,21 @@ class MlDsa:
         return sig_h[:n_ops]
 
 
-class _MusHost:
-    """One mldsa_mus_host (staging chunks, streams, per-batch buffers) on a HotPath's context.  It keeps the HotPath alive;
-    destroying it does not need the context, so it may follow HotPath.close()."""
+class _HostFeed:
+    """One mldsa_ph_host or mldsa_mus_host (staging chunks, streams, per-batch buffers) on a HotPath's context: `loader` is the
+    layer's _*_lib module, `create` / `destroy` its entry points' names.  It keeps the HotPath alive; destroying it does not need
+    the context, so it may follow HotPath.close()."""
 
-    def __init__(self, hp, staging_bytes):
-        self.hp = hp
+    def __init__(self, hp, staging_bytes, loader, create, destroy):
+        self.hp, self.loader, self.destroy = hp, loader, destroy
         out = C.c_void_p(0)
-        _mus_lib.check(_mus_lib.load().mldsa_mus_host_create(hp._h, int(staging_bytes), C.byref(out)))
+        loader.check(getattr(loader.load(), create)(hp._h, int(staging_bytes), C.byref(out)))
         self.handle = out
 
     def __del__(self):
         try:
             if self.handle:
-                _mus_lib.load().mldsa_mus_host_destroy(self.handle)
+                getattr(self.loader.load(), self.destroy)(self.handle)
             self.handle = None
         except Exception:
             pass
@@ -1155,25 +1152,6 @@ class MuStream:
         _mus_lib.check(self.lib.mldsa_mus_final(self.m.hp._h, _ptr(self.state), self.state_bytes, _ptr(mu), _ptr(flag), self.n_ops,
                                                 _stream(self.m.device)))
         return mu[:self.n_ops], flag[:self.n_ops]
-
-
-class _PhHost:
-    """One mldsa_ph_host (staging chunks, streams, per-batch buffers) on a HotPath's context.  It keeps the HotPath alive;
-    destroying it does not need the context, so it may follow HotPath.close()."""
-
-    def __init__(self, hp, staging_bytes):
-        self.hp = hp
-        out = C.c_void_p(0)
-        _ph_lib.check(_ph_lib.load().mldsa_ph_host_create(hp._h, int(staging_bytes), C.byref(out)))
-        self.handle = out
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _ph_lib.load().mldsa_ph_host_destroy(self.handle)
-            self.handle = None
-        except Exception:
-            pass
 
 
 class PrehashStream:

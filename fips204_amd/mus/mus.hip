@@ -13,12 +13,11 @@
 //                  the shorter one.  The lanes that hold a rate word load their own (lo, hi) of each block; (lo, hi) <-> (E, O) at
 //                  load, absorb and store.  Every cross-lane step is executed by the whole wave: what decides a branch around one is
 //                  the same in all 64 lanes.
-// mldsa_mus_host_compute streams [msg_off[0], msg_off[n_ops]) through two staging chunks (mus_chunks.h): chunk i + 1 is uploaded on the
-// copy stream while the update absorbs chunk i on the compute stream, launched for the ops that have bytes in the chunk only, with the
-// chunk as the window of message offsets, so the one offset table uploaded at the start serves every chunk.
+// mldsa_mus_host_compute streams [msg_off[0], msg_off[n_ops]) through the layers' host-memory feed (../layer/host_feed.h): chunk i + 1 is
+// uploaded on the copy stream while the update absorbs chunk i on the compute stream, launched for the ops that have bytes in the chunk
+// only, with the chunk as the window of message offsets, so the one offset table uploaded at the start serves every chunk.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -26,20 +25,14 @@
 
 #include "../../include/mldsa_mus.h"
 #include "../csrc/keccak_coop2.h"
+#include "../layer/host_chunks.h"
+#include "../layer/host_feed.h"
 #include "../layer/layer_dev.h"
 #include "../layer/layer_host.h"
-#include "mus_chunks.h"
 
 struct mldsa_mus_host {
-    int dev = -1;
-    size_t staging = 0;
     std::mutex lock;  // one call at a time
-    hipStream_t copy = nullptr, compute = nullptr;
-    uint8_t* d_stage[2] = {nullptr, nullptr};
-    uint8_t* h_stage[2] = {nullptr, nullptr};
-    hipEvent_t copied[2] = {nullptr, nullptr};  // the chunk is in d_stage[b]
-    hipEvent_t freed[2] = {nullptr, nullptr};   // the update that read d_stage[b] has finished
-    bool in_flight[2] = {false, false};
+    mldsa_layer::HostFeed feed;
     // per-batch buffers, kept and grown: the message offsets, the ctx offsets and ctxs (at most 256 bytes kept per op), the states
     size_t cap_ops = 0;
     uint64_t* d_off = nullptr;
@@ -55,8 +48,8 @@ namespace {
 using namespace mldsa_layer;
 using mldsa::Coop2Lane;
 using mldsa::load_le32;
-using mldsa_mus::piece_hi;
-using mldsa_mus::piece_lo;
+using mldsa_layer::piece_hi;
+using mldsa_layer::piece_lo;
 
 constexpr int RATE = mldsa::SHAKE256_RATE;  // 136
 constexpr int RATE_W = RATE / 8;            // 17 64-bit words
@@ -147,15 +140,6 @@ __device__ __forceinline__ void xor_into_state(uint32_t* sp, size_t S, int pos, 
         pos++;
         len--;
     }
-}
-
-__device__ __forceinline__ size_t wave_max(size_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const size_t o = (size_t)__shfl_xor((unsigned long long)v, m);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // the pad of SHAKE256 on a state that holds `fill` bytes of the current block: 0x1F at byte `fill`, 0x80 on the block's last byte
@@ -450,8 +434,6 @@ int check_state(const char* fn, const mldsa_ctx* ctx, const void* state, size_t 
 }
 
 // ---------------------------------------------------------------------------------------------------------- host-memory call
-constexpr size_t DEFAULT_STAGING = (size_t)64 << 20;  // the staging size of the pre-hash layer's host-memory calls; not swept again here
-
 void release_batch(mldsa_mus_host* h) {
     if (h->d_off) (void)hipFree(h->d_off);
     if (h->d_coff) (void)hipFree(h->d_coff);
@@ -459,18 +441,6 @@ void release_batch(mldsa_mus_host* h) {
     if (h->d_state) (void)hipFree(h->d_state);
     h->d_off = h->d_coff = nullptr, h->d_ctxs = nullptr, h->d_state = nullptr;
     h->cap_ops = 0;
-}
-
-void release(mldsa_mus_host* h) {
-    for (int b = 0; b < 2; b++) {
-        if (h->d_stage[b]) (void)hipFree(h->d_stage[b]);
-        if (h->h_stage[b]) (void)hipHostFree(h->h_stage[b]);
-        if (h->copied[b]) (void)hipEventDestroy(h->copied[b]);
-        if (h->freed[b]) (void)hipEventDestroy(h->freed[b]);
-    }
-    release_batch(h);
-    if (h->copy) (void)hipStreamDestroy(h->copy);
-    if (h->compute) (void)hipStreamDestroy(h->compute);
 }
 
 int reserve(const char* fn, mldsa_mus_host* h, size_t n_ops) {
@@ -486,17 +456,6 @@ int reserve(const char* fn, mldsa_mus_host* h, size_t n_ops) {
     return MLDSA_OK;
 }
 
-// page-locked (or otherwise known to the runtime) host memory is copied by DMA where it lies; anything else goes through the
-// page-locked bounce chunk
-bool is_pinned(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
 #define MUS_HIP(call, what)                                     \
     do {                                                        \
         const hipError_t e_ = (call);                           \
@@ -507,7 +466,8 @@ int stream_mu(const char* fn, mldsa_mus_host* h, int mode, const uint8_t* tr, si
               const uint64_t* msg_off, const uint8_t* ctxs, const uint64_t* ctx_off, uint8_t* mu, int32_t* mu_flag, size_t n_ops) {
     int rc = reserve(fn, h, n_ops);
     if (rc != MLDSA_OK) return rc;
-    MUS_HIP(hipMemcpyAsync(h->d_off, msg_off, 8 * (n_ops + 1), hipMemcpyHostToDevice, h->compute), "upload of msg_off");
+    const hipStream_t s = h->feed.compute;
+    MUS_HIP(hipMemcpyAsync(h->d_off, msg_off, 8 * (n_ops + 1), hipMemcpyHostToDevice, s), "upload of msg_off");
     if (ctx_off) {  // the ctxs packed anew, at most MAX_CTX_KEPT bytes of each: what the device holds of them is bounded by n_ops
         h->h_coff.resize(n_ops + 1);
         h->h_ctxs.clear();
@@ -518,36 +478,20 @@ int stream_mu(const char* fn, mldsa_mus_host* h, int mode, const uint8_t* tr, si
             if (keep) h->h_ctxs.insert(h->h_ctxs.end(), ctxs + ctx_off[i], ctxs + ctx_off[i] + keep);
         }
         h->h_coff[n_ops] = h->h_ctxs.size();
-        MUS_HIP(hipMemcpyAsync(h->d_coff, h->h_coff.data(), 8 * (n_ops + 1), hipMemcpyHostToDevice, h->compute), "upload of ctx_off");
+        MUS_HIP(hipMemcpyAsync(h->d_coff, h->h_coff.data(), 8 * (n_ops + 1), hipMemcpyHostToDevice, s), "upload of ctx_off");
         if (!h->h_ctxs.empty())
-            MUS_HIP(hipMemcpyAsync(h->d_ctxs, h->h_ctxs.data(), h->h_ctxs.size(), hipMemcpyHostToDevice, h->compute), "upload of ctxs");
+            MUS_HIP(hipMemcpyAsync(h->d_ctxs, h->h_ctxs.data(), h->h_ctxs.size(), hipMemcpyHostToDevice, s), "upload of ctxs");
     }
-    rc = launch_init(fn, mode, tr, n_keys, key_idx, ctx_off ? h->d_ctxs : nullptr, ctx_off ? h->d_coff : nullptr, h->d_state, n_ops, h->compute);
+    rc = launch_init(fn, mode, tr, n_keys, key_idx, ctx_off ? h->d_ctxs : nullptr, ctx_off ? h->d_coff : nullptr, h->d_state, n_ops, s);
     if (rc != MLDSA_OK) return rc;
-
-    const bool pinned = msg_off[n_ops] > msg_off[0] && is_pinned(msgs + msg_off[0]);
-    h->in_flight[0] = h->in_flight[1] = false;
-    mldsa_mus::ChunkPlan plan(msg_off, n_ops, h->staging);
-    mldsa_mus::Chunk c;
-    for (int b = 0; plan.next(&c); b ^= 1) {
-        const size_t len = (size_t)(c.hi - c.lo);
-        if (h->in_flight[b]) MUS_HIP(hipEventSynchronize(h->freed[b]), "wait for a staging chunk");  // the only wait of the loop
-        const uint8_t* src = msgs + c.lo;
-        if (!pinned) {
-            memcpy(h->h_stage[b], src, len);
-            src = h->h_stage[b];
-        }
-        MUS_HIP(hipMemcpyAsync(h->d_stage[b], src, len, hipMemcpyHostToDevice, h->copy), "upload of a chunk");
-        MUS_HIP(hipEventRecord(h->copied[b], h->copy), "hipEventRecord");
-        MUS_HIP(hipStreamWaitEvent(h->compute, h->copied[b], 0), "hipStreamWaitEvent");
-        rc = launch_update(fn, h->d_state, h->d_stage[b], h->d_off, n_ops, c.first, c.last - c.first, c.lo, c.hi, c.lo, h->compute);
-        if (rc != MLDSA_OK) return rc;
-        MUS_HIP(hipEventRecord(h->freed[b], h->compute), "hipEventRecord");
-        h->in_flight[b] = true;
-    }
-    rc = launch_final(fn, h->d_state, mu, mu_flag, n_ops, h->compute);
+    const FeedEnd end = h->feed.run(msgs, msg_off, n_ops, [&](const Chunk& c, const uint8_t* d_chunk) {
+        return launch_update(fn, h->d_state, d_chunk, h->d_off, n_ops, c.first, c.last - c.first, c.lo, c.hi, c.lo, s);
+    });
+    if (end.hip != hipSuccess) return hip_failed(fn, end.step, end.hip);
+    if (end.rc != MLDSA_OK) return end.rc;
+    rc = launch_final(fn, h->d_state, mu, mu_flag, n_ops, s);
     if (rc != MLDSA_OK) return rc;
-    MUS_HIP(hipStreamSynchronize(h->compute), "hipStreamSynchronize");
+    MUS_HIP(hipStreamSynchronize(s), "hipStreamSynchronize");
     return MLDSA_OK;
 }
 
@@ -601,18 +545,7 @@ int mldsa_mus_host_create(mldsa_ctx* ctx, size_t staging_bytes, mldsa_mus_host**
     if (!ctx || !out) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
     LAYER_ON_DEVICE(ctx);
     mldsa_mus_host* h = new mldsa_mus_host;
-    h->dev = dev_;
-    h->staging = staging_bytes ? staging_bytes : DEFAULT_STAGING;
-    bool ok = hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->compute, hipStreamNonBlocking) == hipSuccess;
-    for (int b = 0; b < 2 && ok; b++)
-        ok = hipMalloc((void**)&h->d_stage[b], h->staging) == hipSuccess &&
-             hipHostMalloc((void**)&h->h_stage[b], h->staging, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&h->copied[b], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&h->freed[b], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        release(h);
+    if (!h->feed.create(dev_, staging_bytes)) {
         delete h;
         return fail(MLDSA_ERR_NOMEM, std::string(fn) + ": streams, events or staging memory could not be allocated");
     }
@@ -622,11 +555,11 @@ int mldsa_mus_host_create(mldsa_ctx* ctx, size_t staging_bytes, mldsa_mus_host**
 
 void mldsa_mus_host_destroy(mldsa_mus_host* h) {
     if (!h) return;
+    const int dev = h->feed.dev;
+    h->feed.destroy();  // waits for both streams
     {
-        DeviceScope ds(h->dev);
-        if (h->compute) (void)hipStreamSynchronize(h->compute);
-        if (h->copy) (void)hipStreamSynchronize(h->copy);
-        release(h);
+        DeviceScope ds(dev);
+        release_batch(h);
     }
     delete h;
 }
@@ -647,13 +580,10 @@ int mldsa_mus_host_compute(mldsa_mus_host* h, int mode, const uint8_t* tr, size_
     if (!msgs && msg_off[n_ops] != msg_off[0]) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": msg_off names bytes of a NULL msgs");
     if (ctx_off && !ctxs && ctx_off[n_ops] != ctx_off[0]) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": ctx_off names bytes of a NULL ctxs");
     std::lock_guard<std::mutex> guard(h->lock);
-    DeviceScope ds(h->dev);
+    DeviceScope ds(h->feed.dev);
     if (!ds.ok) return fail(MLDSA_ERR_DEVICE, std::string(fn) + ": hipSetDevice failed");
     const int rc = stream_mu(fn, h, mode, tr, n_keys, key_idx, msgs, msg_off, ctxs, ctx_off, mu, mu_flag, n_ops);
-    if (rc != MLDSA_OK) {  // nothing of a failed call stays in flight
-        (void)hipStreamSynchronize(h->copy);
-        (void)hipStreamSynchronize(h->compute);
-    }
+    if (rc != MLDSA_OK) h->feed.drain();  // nothing of a failed call stays in flight
     return rc;
 }
 

@@ -24,6 +24,7 @@
 
 #include "../../include/mldsa_ph.h"
 #include "../csrc/keccak.h"
+#include "../layer/layer_dev.h"
 #include "ph_internal.h"
 #include "sha2_dev.h"
 
@@ -31,6 +32,7 @@ namespace {
 
 using mldsa::KeccakState;
 using mldsa::load_le32;
+using mldsa_layer::wave_max;
 using mldsa_ph::bswap32;
 using mldsa_ph::fail;
 using mldsa_ph::OID_LEN;
@@ -145,15 +147,6 @@ __device__ __forceinline__ void buf_append(uint32_t* buf0, size_t S, int pos, co
         pos++;
         len--;
     }
-}
-
-__device__ __forceinline__ size_t wave_max(size_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const size_t o = (size_t)__shfl_xor((unsigned long long)v, m);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 template <int FAM>

@@ -1,4 +1,4 @@
-// The chunk plan of mldsa_mus_host_compute (fips204_amd/mus/mus_chunks.h) on its own: pure host code, compiled with
+// The chunk plan of the host-memory feed (fips204_amd/layer/host_chunks.h) on its own: pure host code, compiled with
 // -fsanitize=address,undefined and run as a child process by tests/test_mu_stream_cpu.py.  Over seeded offset tables and staging sizes
 // 1, 7, 136, 4096 it checks that every byte of [off[0], off[n]) lies in exactly one chunk, in order; that no chunk exceeds `staging`;
 // that the per-chunk piece offsets are monotone and start at 0; that the op range of a chunk is exactly the ops with bytes in it; that an
@@ -9,11 +9,11 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../../fips204_amd/mus/mus_chunks.h"
+#include "../../fips204_amd/layer/host_chunks.h"
 
-using mldsa_mus::Chunk;
-using mldsa_mus::ChunkPlan;
-using mldsa_mus::piece_off_in_chunk;
+using mldsa_layer::Chunk;
+using mldsa_layer::ChunkPlan;
+using mldsa_layer::piece_off_in_chunk;
 
 static int g_fail = 0;
 #define CHECK(cond)                                                        \

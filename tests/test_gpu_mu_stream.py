@@ -6,9 +6,9 @@ from gpu_common import C, dev, dev_off, hashlib, host, kidx_dev, np, orc, pytest
 
 import mus_cases
 from conftest import PSET
-from fips204_amd import _lib, _mus_lib
+from fips204_amd import _lib, _mus_lib, _ph_lib
 from fips204_amd.hotpath import _ptr, _stream
-from fips204_amd.ml_dsa import MODE_INTERNAL, MODE_PREHASH, MODE_PURE, PublicKeys, _cat_with_offsets, external_mu
+from fips204_amd.ml_dsa import MODE_INTERNAL, MODE_PREHASH, MODE_PURE, MlDsa, PublicKeys, _cat_with_offsets, external_mu
 from mus_cases import HOST_LENS, hashlib_incremental, pieces_of
 
 pytestmark = pytest.mark.gpu
@@ -428,6 +428,68 @@ def test_host_fed_refusals(sets):
                                     _ptr(fl), n)
     assert rc == _lib.OK and host(fl).tolist() == [0] * b["nk"] + [2] * (n - b["nk"]) and not host(out)[b["nk"]:].any()
     assert [r.tobytes() for r in host(out)[:b["nk"]]] == [external_mu(tr_h[i], b["msgs"][i]) for i in range(b["nk"])]
+
+
+# The smallest shape that puts chunk ends on message ends, through both host-memory feeds (mu here, HashML-DSA in the pre-hash layer).
+# With 256-byte staging the chunks are [0, 256) [256, 512) [512, 768) [768, 777): message 1 ends exactly on a chunk end, two empty
+# messages sit on that boundary, message 4 starts on it and spans three chunks, an empty message ends the batch.  256 is at least every
+# pre-hash block or rate, so nothing below one block per chunk is relied on.
+EDGE_LENS = [0, 256, 0, 0, 520, 1, 0]
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+def test_host_feeds_with_chunk_ends_on_message_ends(sets, pinned):
+    m = MlDsa(44, hotpath=sets[44].hp)  # an object of its own: the handles below are created here and grow here
+    staging, n, nk = 256, len(EDGE_LENS), 3
+    rng = np.random.default_rng(256)
+    msgs = [rng.integers(0, 256, k, dtype=np.uint8).tobytes() for k in EDGE_LENS]
+    rnd = [hashlib.sha256(b"edge-rnd" + bytes([i])).digest() for i in range(n)]
+    rn = np.frombuffer(b"".join(rnd), dtype=np.uint8)
+    pk, sk = m.keygen_from_seed([hashlib.sha256(b"edge-key" + bytes([j])).digest() for j in range(nk)])
+    pk_h, sk_h = host(pk).copy(), host(sk).copy()
+    kidx = (np.arange(n) % nk).astype(np.uint32)
+    tr_d = m.public_keys_from_bytes(pk).tr.clone()
+    tr_h = [r.tobytes() for r in host(tr_d)]
+    sks = m.private_keys_from_bytes(sk)
+    want_mu = [external_mu(tr_h[kidx[i]], msgs[i]) for i in range(n)]
+    want_sig = {ph: [r.tobytes() for r in host(m.try_hash_sign_with_seed(sks, msgs, rnd, ph=ph, key_idx=kidx, prehash="host"))]
+                for ph in ("SHA512", "SHAKE128")}
+    keep = []
+    flat, off = in_host_memory(msgs, pinned, keep)
+    assert off.tolist() == [0, 0, 256, 256, 256, 776, 777, 777]
+
+    def this_call(ops=n):
+        """the first `ops` ops through mu_host, hash_sign_host and hash_verify_host: (mu rows, {ph: signatures})"""
+        o = off[:ops + 1]
+        mu, flag = m.mu_host(tr_d, (flat, o), None, kidx[:ops], MODE_PURE, staging)
+        assert not host(flag).any()
+        sigs = {}
+        for ph in want_sig:
+            sig = m.hash_sign_host(sk_h, (flat, o), rn[:32 * ops], ph=ph, key_idx=kidx[:ops], staging_bytes=staging)
+            assert m.hash_verify_host(pk_h, (flat, o), sig, ph=ph, key_idx=kidx[:ops], staging_bytes=staging).all(), ph
+            sigs[ph] = [r.tobytes() for r in sig]
+        return [r.tobytes() for r in host(mu)], sigs
+
+    # a call of 3 ops first, then the whole batch on the same handles: the per-call buffers grow
+    mu3, sig3 = this_call(3)
+    assert mu3 == want_mu[:3] and all(sig3[ph] == want_sig[ph][:3] for ph in want_sig)
+    first = this_call()
+    assert first[0] == want_mu and first[1] == want_sig
+    # a call refused for a decreasing msg_off on each handle, then the batch again: identical results
+    bad = off.copy()
+    bad[5] = bad[4] - np.uint64(1)
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    mus, ph_lib = _mus_lib.load(), _ph_lib.load()
+    out = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+    kd = kidx_dev(kidx)
+    torch.cuda.synchronize()
+    assert mus.mldsa_mus_host_compute(m._mus_host(staging), MODE_PURE, _ptr(tr_d), nk, _ptr(kd), ptr(flat), ptr(bad), NULL, NULL, _ptr(out), NULL,
+                                      n) == _lib.ERR_PARAM
+    sg, okb = np.frombuffer(b"".join(want_sig["SHA512"]), dtype=np.uint8), np.full(n, 7, dtype=np.uint8)
+    assert ph_lib.mldsa_hash_verify_host(m._ph_host(staging), 44, m._ph_arg("SHA512"), ptr(pk_h), nk, ptr(kidx), ptr(flat), ptr(bad), NULL, NULL,
+                                         ptr(sg), ptr(okb), n) == _lib.ERR_PARAM
+    assert not host(out).any() and (okb == 7).all()
+    assert this_call() == first
 
 
 # ----------------------------------------------------------------------------------------------------------- 6. many ops

@@ -1,4 +1,4 @@
-"""What the layered libraries share (fips204_amd/layer/: layer_host.h, layer_dev.h, layer.mk) -- CPU only.
+"""What the layered libraries share (fips204_amd/layer/: layer_host.h, layer_dev.h, layer.mk, host_feed.h, host_chunks.h) -- CPU only.
 
 The five libraries (ph, keys, mu, seed, keycheck) are loaded into one process.  The shared host scaffold must therefore stay private to
 each of them: an error slot per library, and no symbol of the scaffold in any dynamic symbol table.
@@ -15,7 +15,7 @@ from fips204_amd import _keycheck_lib, _keys_lib, _lib, _mu_lib, _ph_lib, _seed_
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fips204_amd")
 LAYER_DIR = os.path.join(PKG, "layer")
-SHARED = [os.path.join(LAYER_DIR, f) for f in ("layer_host.h", "layer_dev.h", "layer.mk")]
+SHARED = [os.path.join(LAYER_DIR, f) for f in ("layer_host.h", "layer_dev.h", "layer.mk", "host_feed.h", "host_chunks.h")]
 LOADERS = {"ph": _ph_lib, "keys": _keys_lib, "mu": _mu_lib, "seed": _seed_lib, "keycheck": _keycheck_lib}
 
 _STRING_CTOR = "_ZNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEC2IS3_EEPKcRKS3_"
@@ -161,7 +161,34 @@ def test_one_scaffold_only():
         for word in ("int fail(", "int core_failed(", "int hip_failed(", "bool aligned(", "struct Taker", "auto take = ", "_CORE(call, name)",
                      "_LAUNCHED(what)", "hipSetDevice"):
             assert word not in t, (rel, word)
+    # one host-memory feed: the ring of staging chunks is written in layer/host_feed.h and nowhere else among the layers (csrc/ aside)
+    feed_words = {"bool is_pinned(": [], "in_flight": [], "DEFAULT_STAGING": []}
+    for root, _, files in os.walk(PKG):
+        if os.path.relpath(root, PKG).split(os.sep)[0] == "csrc":
+            continue
+        for f in files:
+            if f.endswith((".hip", ".h", ".hpp", ".cpp")):
+                text = open(os.path.join(root, f), errors="replace").read()
+                for word, where in feed_words.items():
+                    if word in text:
+                        where.append(os.path.relpath(os.path.join(root, f), PKG))
+    for word, where in feed_words.items():
+        assert where == [os.path.join("layer", "host_feed.h")], (word, where)
+    for rel in ("ph/hostfed.hip", "mus/mus.hip"):
+        assert '#include "../layer/host_feed.h"' in open(os.path.join(PKG, rel)).read(), rel
     # five Makefiles, one recipe
     for layer in LOADERS:
         mk = open(os.path.join(PKG, layer, "Makefile")).read()
         assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk, layer
+
+
+def test_the_host_feed_under_asan_and_ubsan(tmp_path):
+    """layer/host_feed.h, compiled host-only as tests/test_sanitizers_cpu.py compiles the core's host code and linked over the stand-in
+    HIP runtime, driven by tests/cpp/host_feed_main.cpp: a stand-alone program, so the sanitizers' runtimes are linked in"""
+    exe = str(tmp_path / "host_feed")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Werror", "-Wno-unused-function", "-x", "hip",
+                           os.path.join(ROOT, "tests", "cpp", "host_feed_main.cpp"), os.path.join(ROOT, "tests", "cpp", "stub_hip_full.cpp"),
+                           "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert run.returncode == 0 and "host_feed OK" in run.stdout, run.stderr[-2000:]

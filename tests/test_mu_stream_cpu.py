@@ -15,7 +15,7 @@ from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_e
                           layered_on_core, links_the_core_and_never_builds_it, sources_clean)
 
 MUS_DIR = os.path.join(ROOT, "fips204_amd", "mus")
-SOURCES = ["Makefile", "mus.hip", "mus_chunks.h"]
+SOURCES = ["Makefile", "mus.hip"]
 
 
 @pytest.fixture(scope="module")
@@ -166,16 +166,18 @@ def test_kernels_do_not_spill_and_sources_are_clean(mus):
     for stem in ("k_mus_init_lane", "k_mus_update_lane", "k_mus_final_lane", "k_mus_init_wave", "k_mus_update_wave", "k_mus_final_wave"):
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) >= 6
-    read = sources_clean(MUS_DIR, ["../../include/mldsa_mus.h", "../_mus_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"], asm_free=True)
+    read = sources_clean(MUS_DIR, ["../../include/mldsa_mus.h", "../_mus_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h", "../layer/host_feed.h",
+                               "../layer/host_chunks.h"], asm_free=True)
     src = includes_the_core_device_headers(MUS_DIR, "mus.hip")
-    assert '#include "../layer/layer_host.h"' in src and '#include "../csrc/keccak_coop2.h"' in src and '#include "mus_chunks.h"' in src
+    assert '#include "../layer/layer_host.h"' in src and '#include "../csrc/keccak_coop2.h"' in src and '#include "../layer/host_chunks.h"' in src
+    assert '#include "../layer/host_feed.h"' in src
     # the scaffold is the layers' shared one; no spin waits, no atomics, no wave sleeps
     for f, t in read:
-        if f in ("mus.hip", "mus_chunks.h"):
+        if f in ("mus.hip", "../layer/host_chunks.h"):
             for word in ("struct DeviceScope", "thread_local", "int fail(", "atomic", "s_sleep", "__builtin_amdgcn_s_", "while (true)", "volatile"):
                 assert word not in t, (f, word)
     # the chunk plan has no HIP in it, and the kernels clip by its two functions
-    plan = dict(read)["mus_chunks.h"]
+    plan = dict(read)["../layer/host_chunks.h"]
     assert "hip" not in re.sub(r"//[^\n]*", "", plan).lower() and "__device__" not in plan and "__global__" not in plan
     assert src.count("piece_lo(p0, win_lo)") == 2 and src.count("piece_hi(p1, win_hi)") == 2
     # the wave form runs on the core's interleaved cooperative sponge, converted at load, absorb and store
@@ -219,6 +221,6 @@ def test_the_chunk_plan_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "mus_chunks")
     cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "mus_chunks_main.cpp")])
+                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "host_chunks_main.cpp")])
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "mus_chunks OK" in run.stdout, run.stderr[-2000:]

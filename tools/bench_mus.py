@@ -51,7 +51,7 @@ def build_form(forms_dir, name, value):
             os.symlink(target, link)
     so = os.path.join(shadow, "libmldsa_mus.so")
     if not os.path.exists(so):
-        for f in ("Makefile", "mus.hip", "mus_chunks.h"):
+        for f in ("Makefile", "mus.hip"):
             shutil.copy(os.path.join(build.MUS_DIR, f), os.path.join(shadow, f))
         flags = f"-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DMLDSA_MUS_WAVE_MAX_OPS={value}"
         subprocess.run(["make", "-C", shadow, f"CXXFLAGS={flags}"], check=True, capture_output=True)
