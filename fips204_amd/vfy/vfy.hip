@@ -2,9 +2,12 @@
 // layered on the core's C ABI and rebuilt around three levers:
 //   - ExpandA on the folded Keccak round of keccak180.h (180 VALU per round instead of 190): the kernel is bound by its own instruction
 //     count, so fewer instructions are the only thing that moves it;
-//   - parts: the call is cut into parts (vfy_parts.h); ExpandA of part p + 1 runs on one library-owned stream while k_verify_main and
-//     the c~ hash of part p run on the other, and the front of every part (key-index check, mu, SampleInBall) on the caller's stream
-//     underneath.  Only stream events order the work.  The A_hat scratch is a ring of two parts.
+//   - parts: the call is cut into parts (vfy_parts.h).  A call of one part -- every call up to MLDSA_VFY_PART_OPS ops -- is one chain on
+//     the caller's stream: ExpandA, k_verify_main, the c~ hash, with the front (key-index check, mu, SampleInBall) on one library-owned
+//     stream beside ExpandA and no hand-over between queues on the way.  In a call of several parts ExpandA of part p + 1 runs on one
+//     library-owned stream while k_verify_main and the c~ hash of part p run on the other, and the front of every part on the caller's
+//     stream underneath.  The order of either shape is data (order_plan() in vfy_parts.h), enqueue() below walks it; only stream
+//     events order the work.  The A_hat scratch is a ring of two parts.
 //   - k_verify_main's VALU stream: two rows a trip on two register sets, hint bits read from LDS, quad exchanges without a zeroed
 //     destination, w1Encode with one gather ("wave helpers of verify_main" below): the kernel is bound by instruction issue as well.
 // The device building blocks are the core's, included read-only (field.h, keccak.h, sampler_dev.h, ntt_wave.h, rounding.h, verify_dev.h,
@@ -510,7 +513,7 @@ using namespace mldsa_vfy;
 struct DevState {
     int dev = -1;
     int n_cu = 256;
-    hipStream_t ea = nullptr, vm = nullptr;  // ExpandA of the parts | verify_main and the c~ hash of the parts
+    hipStream_t ea = nullptr, vm = nullptr;  // several parts: ExpandA | verify_main and the c~ hash.  One part: unused | the front
     std::vector<hipEvent_t> ev;              // ordering events, handed out per call from the front
     Twiddle *fwd = nullptr, *inv = nullptr;
     bool prof_on = false;
@@ -648,15 +651,23 @@ struct Call {
     size_t n_ops;
 };
 
-// Enqueues the whole call (g_mutex held, the device current).  Streams: `s` the caller's, d->ea, d->vm -- three in flight.
+// Enqueues the whole call (g_mutex held, the device current): order_plan() of vfy_parts.h says on which lane every stage of every part
+// runs and which events order the lanes; this function walks the plan and issues one runtime call per step.  Lanes: `s` the caller's
+// stream, d->ea, d->vm.
+// One part (every call up to MLDSA_VFY_PART_OPS ops): one chain on the caller's stream, the front beside it -- two streams in flight.
+//   s:     fork | ExpandA | waits for the front | verify_main | c~ hash and verdict
+//   d->vm: waits for the fork | key-index check, mu, SampleInBall | front
+//   (a cross-queue hand-over costs about 10 us, section 4 of DESIGN.md: with ExpandA, verify_main and the c~ hash on the library's streams
+//   a call paid three of them on its critical path; here the one wait left completes at about the time ExpandA does)
+// Several parts: three in flight.
 //   s:     fork | per part: key-index check, mu, SampleInBall, front[p] | ... | waits for the join
-//   d->ea: per part p: waits for used[p - 2] (the ring half is free), ExpandA, ready[p]
-//   d->vm: per part p: waits for ready[p] and front[p], verify_main, used[p], c~ hash and verdict | join
+//   d->ea: waits for the fork | per part p: waits for used[p - 2] (the ring half is free), ExpandA, ready[p]
+//   d->vm: per part p: waits for ready[p] and front[p], verify_main, used[p] (when a part p + 2 follows), c~ hash and verdict | join
 int enqueue(const char* fn, DevState* d, const Call& c, uint8_t* scratch, hipStream_t s) {
     const mldsa_params& p = c.p;
     const PartPlan plan(c.n_ops, part_ops());
     const Carve cv = carve(p.k, p.l, (size_t)p.w1_len, plan);
-    const size_t mw = 64 + (size_t)p.w1_len, n_parts = plan.n_parts();
+    const size_t mw = 64 + (size_t)p.w1_len;
     uint32_t* c8 = reinterpret_cast<uint32_t*>(scratch + cv.c);
     int32_t* znorm = reinterpret_cast<int32_t*>(scratch + cv.znorm);
     int32_t* hvalid = reinterpret_cast<int32_t*>(scratch + cv.hvalid);
@@ -666,88 +677,83 @@ int enqueue(const char* fn, DevState* d, const Call& c, uint8_t* scratch, hipStr
     uint8_t* mu_w1 = scratch + cv.mu_w1;
     const size_t sig_len = (size_t)p.sig_len;
 
+    const OrderPlan order = order_plan(plan.n_parts());
+    const hipStream_t lanes[N_LANES] = {s, d->ea, d->vm};
     Events evs(d);
-    hipEvent_t fork = evs.next(), join = evs.next();
-    std::vector<hipEvent_t> ready(n_parts), used(n_parts), front(n_parts);
-    for (size_t i = 0; i < n_parts; i++) {
-        ready[i] = evs.next();
-        used[i] = evs.next();
-        front[i] = evs.next();
-    }
+    std::vector<hipEvent_t> ev(order.n_events);
+    for (hipEvent_t& e : ev) e = evs.next();
     if (evs.err != hipSuccess) return hip_failed(fn, "creating an event", evs.err);
 
-    VFY_HIP(hipEventRecord(fork, s), "recording the fork");
-    VFY_HIP(hipStreamWaitEvent(d->ea, fork, 0), "ordering the ExpandA stream behind the caller's");
-    VFY_HIP(hipStreamWaitEvent(d->vm, fork, 0), "ordering the arithmetic stream behind the caller's");
-    for (size_t i = 0; i < n_parts; i++) {
-        const Part part = plan.at(i);
+    for (const Step& st : order.steps) {
+        const hipStream_t q = lanes[st.lane];
+        if (st.act == ACT_RECORD) {
+            VFY_HIP(hipEventRecord(ev[st.n], q), (std::string("recording ") + st.what).c_str());
+            continue;
+        }
+        if (st.act == ACT_WAIT) {
+            VFY_HIP(hipStreamWaitEvent(q, ev[st.n], 0), (std::string("waiting for ") + st.what).c_str());
+            continue;
+        }
+        const Part part = plan.at(st.n);
         const size_t o = part.first, n = part.count;
         const size_t key_base = c.key_idx ? 0 : o;  // identity mapping: op i uses key i
         int32_t* a_hat = reinterpret_cast<int32_t*>(scratch + cv.ring[part.half]);
         const uint8_t* sg = c.sigs + o * sig_len;
-        // ---- ExpandA of the part, as soon as the part that used this ring half has read it
-        if (i >= 2) VFY_HIP(hipStreamWaitEvent(d->ea, used[i - 2], 0), "waiting for the ring half");
-        {
-            ProfScope ps(d, d->ea, "expand_a");
-            launch_expand_a(c.set, c.rho + key_base * 32, c.key_idx ? c.key_idx + o : nullptr, a_hat, n, c.key_idx ? (uint32_t)c.n_keys : 0u, d->ea);
+        // the key index k_sanitize_keys leaves for the part, and its flags
+        const uint32_t* kp = c.key_idx ? kidx + o : nullptr;
+        const int32_t* kb = c.key_idx ? key_bad + o : nullptr;
+        switch (st.stage) {
+        case STAGE_EXPAND_A: {
+            ProfScope ps(d, q, "expand_a");
+            launch_expand_a(c.set, c.rho + key_base * 32, c.key_idx ? c.key_idx + o : nullptr, a_hat, n, c.key_idx ? (uint32_t)c.n_keys : 0u, q);
+            break;
         }
-        LAYER_LAUNCHED("k_expand_a launch");
-        VFY_HIP(hipEventRecord(ready[i], d->ea), "recording ExpandA's end");
-        // ---- the front of the part on the caller's stream, underneath ExpandA.  (Five ExpandA waves leave a SIMD 32 VGPRs, so
-        // SampleInBall's waves get a slot only as ExpandA's drain: it ends with ExpandA, 1.06 ms instead of 0.19.  Launching the front
-        // ahead of ExpandA, SampleInBall on the arithmetic stream, brought it to 0.04 ms and made the call 1-2 % SLOWER in the
-        // same-box alternation: not kept.)
-        const uint32_t* kp = nullptr;
-        const int32_t* kb = nullptr;
-        if (c.key_idx) {
-            hipLaunchKernelGGL(k_sanitize_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.key_idx + o, (uint32_t)c.n_keys, n, kidx + o, key_bad + o);
-            kp = kidx + o;
-            kb = key_bad + o;
-        }
-        {
-            ProfScope ps(d, s, "mu");
-            hipLaunchKernelGGL(k_mu, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, c.tr + key_base * 64, (size_t)64, kp, c.mode, c.msgs, c.msg_off, c.ctxs,
-                               c.ctx_off, mu_w1 + o * mw, mw, ctx_bad + o, kb, n, o, c.n_ops);
-        }
-        {
-            ProfScope ps(d, s, "sample_in_ball");
-            const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-#define VFY_SIB(KK, LL, GB, G2, CT, MW) hipLaunchKernelGGL((k_sample_in_ball<CT>), grid, block, 0, s, sg, sig_len, p.tau, c8 + o * 64, n)
-            VFY_BY_SET(c.set, VFY_SIB);
+        // ---- the front of the part, beside ExpandA and enqueued behind it.  (Five ExpandA waves leave a SIMD 32 VGPRs, so SampleInBall's
+        // waves get a slot only as ExpandA's drain: it ends with ExpandA, 1.06 ms instead of 0.19.  Launching the front ahead of ExpandA,
+        // SampleInBall on the arithmetic stream, brought it to 0.04 ms and made the call 1-2 % SLOWER in the same-box alternation: not
+        // kept.)
+        case STAGE_FRONT: {
+            if (c.key_idx)
+                hipLaunchKernelGGL(k_sanitize_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, c.key_idx + o, (uint32_t)c.n_keys, n, kidx + o, key_bad + o);
+            {
+                ProfScope ps(d, q, "mu");
+                hipLaunchKernelGGL(k_mu, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, q, c.tr + key_base * 64, (size_t)64, kp, c.mode, c.msgs, c.msg_off, c.ctxs,
+                                   c.ctx_off, mu_w1 + o * mw, mw, ctx_bad + o, kb, n, o, c.n_ops);
+            }
+            {
+                ProfScope ps(d, q, "sample_in_ball");
+                const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+#define VFY_SIB(KK, LL, GB, G2, CT, MW) hipLaunchKernelGGL((k_sample_in_ball<CT>), grid, block, 0, q, sg, sig_len, p.tau, c8 + o * 64, n)
+                VFY_BY_SET(c.set, VFY_SIB);
 #undef VFY_SIB
+            }
+            break;
         }
-        LAYER_LAUNCHED("front launch");
-        VFY_HIP(hipEventRecord(front[i], s), "recording the front's end");
-        // ---- the arithmetic and the verdict of the part
-        VFY_HIP(hipStreamWaitEvent(d->vm, ready[i], 0), "waiting for ExpandA");
-        VFY_HIP(hipStreamWaitEvent(d->vm, front[i], 0), "waiting for the front");
-        {
-            ProfScope ps(d, d->vm, "verify_main");
+        case STAGE_VERIFY_MAIN: {
+            ProfScope ps(d, q, "verify_main");
             const size_t need = (n + VW - 1) / VW, cap = (size_t)d->n_cu * 16;  // the core's grid_for(.., VW, 16)
             const dim3 grid((unsigned)(need < cap ? need : cap)), block(64 * VW);
 #define VFY_VM(KK, LL, GB, G2, CT, MW)                                                                                                         \
-    hipLaunchKernelGGL((k_verify_main<KK, LL, GB, G2, MW>), grid, block, 0, d->vm, reinterpret_cast<const uint32_t*>(a_hat), sg, sig_len,      \
+    hipLaunchKernelGGL((k_verify_main<KK, LL, GB, G2, MW>), grid, block, 0, q, reinterpret_cast<const uint32_t*>(a_hat), sg, sig_len,          \
                        p.ctilde_len, c8 + o * 64, c.t1, kp, key_base, hvalid + o, p.omega, mu_w1 + o * mw + 64, mw, znorm + o, p.gamma1 - p.beta, n, \
                        d->fwd, d->inv)
             VFY_BY_SET(c.set, VFY_VM);
 #undef VFY_VM
+            break;
         }
-        LAYER_LAUNCHED("k_verify_main launch");
-        VFY_HIP(hipEventRecord(used[i], d->vm), "recording the end of the ring half's use");
-        {
-            ProfScope ps(d, d->vm, "ctilde_hash");
+        default: {  // STAGE_CTILDE
+            ProfScope ps(d, q, "ctilde_hash");
             const dim3 grid((unsigned)((n + CBLOCK - 1) / CBLOCK)), block(CBLOCK);
 #define VFY_CT(KK, LL, GB, G2, CT, MW)                                                                                                    \
-    hipLaunchKernelGGL((k_ctilde_verdict<CT>), grid, block, 0, d->vm, mu_w1 + o * mw, mw, sg, sig_len, znorm + o, p.gamma1 - p.beta, hvalid + o, \
+    hipLaunchKernelGGL((k_ctilde_verdict<CT>), grid, block, 0, q, mu_w1 + o * mw, mw, sg, sig_len, znorm + o, p.gamma1 - p.beta, hvalid + o, \
                        ctx_bad + o, c.ok + o, n)
             VFY_BY_SET(c.set, VFY_CT);
 #undef VFY_CT
+            break;
         }
-        LAYER_LAUNCHED("k_ctilde_verdict launch");
+        }
+        LAYER_LAUNCHED(st.what);
     }
-    // the last ExpandA precedes the last verify_main through ready[]: the arithmetic stream's end is the call's end
-    VFY_HIP(hipEventRecord(join, d->vm), "recording the join");
-    VFY_HIP(hipStreamWaitEvent(s, join, 0), "joining the caller's stream");
     return MLDSA_OK;
 }
 

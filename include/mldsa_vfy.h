@@ -4,8 +4,11 @@
  * the caller's stream.  It differs in how the pass is run:
  *   - ExpandA, which is 70 % of such a call and bound by its own instruction count, runs on a Keccak round of 180 instead of 190
  *     vector instructions (fips204_amd/vfy/keccak180.h);
- *   - the call is cut into parts: ExpandA of part p + 1 runs on one library-owned stream while the arithmetic and the c~ hash of part
- *     p run on another, ordered by stream events only, so the A_hat scratch is a ring of two parts instead of one row set per op;
+ *   - the call is cut into parts of MLDSA_VFY_PART_OPS ops.  A call of one part -- every call up to that size -- is one chain on the
+ *     caller's stream (ExpandA, the arithmetic, the c~ hash) with the key-index check, mu and SampleInBall on one library-owned stream
+ *     beside ExpandA.  In a call of several parts ExpandA of part p + 1 runs on one library-owned stream while the arithmetic and the c~
+ *     hash of part p run on another, and the A_hat scratch is a ring of two parts instead of one row set per op.  Stream events alone
+ *     order the streams, and the caller's stream ends behind all of the call either way;
  *   - the scratch is the caller's.
  * A_hat is derived again for every op, key table or not, as mldsa_verify does.
  * The formats are the core's: A_hat in the packed 24-bit form (768 bytes per polynomial), c as one byte per coefficient, rows of
@@ -33,8 +36,9 @@ extern "C" {
 #define MLDSA_VFY_ABI_VERSION 1
 /* most operations of one call */
 #define MLDSA_VFY_MAX_OPS ((size_t)1 << 22)
-/* Ops of one part.  A call of at most this many ops is one part.  Measured among call / {1, 2, 4, 8} at 65 536 and 131 072 ops
- * (profiles/vfy_layer_ab.jsonl). */
+/* Ops of one part.  A call of at most this many ops is one part, and runs as one chain on the caller's stream
+ * (profiles/vfy_chain_ab.jsonl).  Measured among call / {1, 2, 4, 8} at 65 536 and 131 072 ops (profiles/vfy_layer_ab.jsonl, DESIGN.md
+ * section 6). */
 #ifndef MLDSA_VFY_PART_OPS
 #define MLDSA_VFY_PART_OPS 65536
 #endif
