@@ -5,7 +5,8 @@ offset-table corruptions and the fuzz-derived batches.
 Imported whole (`from gpu_common import *`) by test_gpu_keys / _boundary / _group / _host_api / _sign_schedule / _seams /
 _baseline_configs / _prehash / _prehash_stream / _prehash_fips_list / _keys_dedup / _external_mu / _seed_keys / _keycheck / _ct0_bound /
 _sign_long_tail / _rare_sampler_paths, and by name (`hp`, `host`, `dev` where theirs were the same) by test_gpu_poly / _samplers /
-_codec_seams / _sign_keygen / _stress / _batcher."""
+_codec_seams / _sign_keygen / _stress / _batcher / vfy_calls.  The three test_gpu_vfy_*.py files import it whole and take their calls
+from vfy_calls by name; the layout of an encoded signature is sig_cases'."""
 import ctypes as C  # noqa: F401
 import hashlib
 import os  # noqa: F401
@@ -18,6 +19,7 @@ import torch
 
 from conftest import PSET  # noqa: F401
 from oracle import oracle as orc
+from sig_cases import sections
 
 @pytest.fixture(scope="module")
 def hp():
@@ -143,8 +145,7 @@ def fuzz_batch(m, pset, n, nk, seed):
     pk_all = np.concatenate([host(pk), rng.integers(0, 256, (nk, m.PK_LEN), dtype=np.uint8)])
     cls = np.arange(n) % len(CLASSES)
     L = m.SIG_LEN
-    cb = 18 if p.gamma1 == (1 << 17) else 20
-    z0, h0 = p.ctilde_len, p.ctilde_len + p.l * 32 * cb  # sigEncode sections: c~ | z | hints (encodings.rs:238-276)
+    _, z0, h0 = sections(p)
     def xor_mask(rows, lo, hi, density):
         mask = (rng.random((rows.size, hi - lo, 8)) < density)
         sig[rows, lo:hi] ^= np.packbits(mask, axis=2, bitorder="little")[:, :, 0]

@@ -206,6 +206,23 @@ def includes_the_core_device_headers(layer_dir, source):
     return src
 
 
+def sanitized_program(tmp_path, name, sources, ok_line, hip_host=False, env=None):
+    """tests/cpp/<sources> compiled into the stand-alone program `name` under ASan + UBSan (with hip_host: host-only by hipcc, as
+    tests/test_sanitizers_cpu.py compiles the core's host code) and run as a child: it ends with status 0 and prints `ok_line`.  `env`
+    is added to the child's environment; nothing else is set there."""
+    exe = str(tmp_path / name)
+    src = [os.path.join(ROOT, "tests", "cpp", f) for f in sources]
+    if hip_host:
+        cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Werror", "-Wno-unused-function", "-x", "hip"] + src + ["-o", exe]
+    else:
+        cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
+        cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror", "-o", exe] + src
+    subprocess.check_call(cmd)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=None if env is None else dict(os.environ, **env))
+    assert run.returncode == 0 and ok_line in run.stdout, (run.stdout[-500:], run.stderr[-4000:])
+
+
 def aligned_buffer():
     """(the buffer to keep alive, a 256-byte aligned pointer into it with 3840 bytes behind it, that pointer + 8)"""
     buf = (C.c_uint8 * 4096)()

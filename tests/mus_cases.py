@@ -10,6 +10,9 @@ import hashlib
 
 import numpy as np
 
+import piece_schedules
+from piece_schedules import gather_pieces, random_cuts  # noqa: F401
+
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
 MODES = (MODE_PURE, MODE_INTERNAL, MODE_PREHASH)
 R = 136
@@ -107,7 +110,7 @@ def coverage(ops_, sched, mode):
 
 def pieces_of(ops_, ops, cuts, u):
     """update u of a schedule as byte strings, one per op of the schedule"""
-    return [ops_[i][1][cs[u]:cs[u + 1]] for i, cs in zip(ops, cuts)]
+    return piece_schedules.pieces_of([msg for _, msg in ops_], ops, cuts, u)
 
 
 def hashlib_incremental(ops_, trs, mode, ops, cuts, upto=None):
@@ -130,20 +133,3 @@ def pack_at(pieces, shift):
     np.cumsum([len(p) for p in pieces], out=off[1:])
     off += np.uint64(shift)
     return np.frombuffer(bytes(shift) + b"".join(pieces) + bytes(8), dtype=np.uint8), off
-
-
-def random_cuts(lens, n_updates, rng):
-    """[n, n_updates + 1] cut positions for messages of the given lengths, vectorised"""
-    n = lens.size
-    inner = np.sort(rng.integers(0, lens[:, None] + 1, (n, n_updates - 1)), axis=1) if n_updates > 1 else np.zeros((n, 0), dtype=np.int64)
-    return np.concatenate([np.zeros((n, 1), dtype=np.int64), inner, lens[:, None].astype(np.int64)], axis=1)
-
-
-def gather_pieces(buf, off, cuts, u):
-    """(flat, offsets) of update u: piece i = buf[off[i] + cuts[i, u] : off[i] + cuts[i, u + 1]], packed back to back"""
-    start = off[:-1].astype(np.int64) + cuts[:, u]
-    plen = cuts[:, u + 1] - cuts[:, u]
-    poff = np.zeros(plen.size + 1, dtype=np.uint64)
-    np.cumsum(plen, out=poff[1:])
-    idx = np.repeat(start - poff[:-1].astype(np.int64), plen) + np.arange(int(poff[-1]), dtype=np.int64)
-    return buf[idx], poff

@@ -8,6 +8,8 @@ import hashlib
 
 import numpy as np
 
+from piece_schedules import gather_pieces, pieces_of, random_cuts  # noqa: F401
+
 PHS = ("SHA256", "SHA512", "SHAKE128")
 BLOCK = {"SHA256": 64, "SHA512": 128, "SHAKE128": 168}
 EDGES = {"SHA256": (0, 1, 55, 56, 63, 64, 65, 119, 120), "SHA512": (111, 112, 127, 128, 239, 240), "SHAKE128": (167, 168, 169, 335, 336)}
@@ -69,11 +71,6 @@ def coverage(msgs, sched, ph):
     return c
 
 
-def pieces_of(msgs, ops, cuts, u):
-    """update u of a schedule as byte strings, one per op"""
-    return [msgs[i][cs[u]:cs[u + 1]] for i, cs in zip(ops, cuts)]
-
-
 def hashlib_incremental(msgs, ops, cuts, ph):
     """hashlib fed the same pieces: the digests the device must reach"""
     new = {"SHA256": hashlib.sha256, "SHA512": hashlib.sha512, "SHAKE128": hashlib.shake_128}[ph]
@@ -84,20 +81,3 @@ def hashlib_incremental(msgs, ops, cuts, ph):
             h.update(msgs[i][cs[u]:cs[u + 1]])
         out.append(h.digest(32) if ph == "SHAKE128" else h.digest())
     return out
-
-
-def random_cuts(lens, n_updates, rng):
-    """[n, n_updates + 1] cut positions for messages of the given lengths, vectorised (65 536 ops)"""
-    n = lens.size
-    inner = np.sort(rng.integers(0, lens[:, None] + 1, (n, n_updates - 1)), axis=1) if n_updates > 1 else np.zeros((n, 0), dtype=np.int64)
-    return np.concatenate([np.zeros((n, 1), dtype=np.int64), inner, lens[:, None].astype(np.int64)], axis=1)
-
-
-def gather_pieces(buf, off, cuts, u):
-    """(flat, offsets) of update u: piece i = buf[off[i] + cuts[i, u] : off[i] + cuts[i, u + 1]], packed back to back"""
-    start = off[:-1].astype(np.int64) + cuts[:, u]
-    plen = cuts[:, u + 1] - cuts[:, u]
-    poff = np.zeros(plen.size + 1, dtype=np.uint64)
-    np.cumsum(plen, out=poff[1:])
-    idx = np.repeat(start - poff[:-1].astype(np.int64), plen) + np.arange(int(poff[-1]), dtype=np.int64)
-    return buf[idx], poff

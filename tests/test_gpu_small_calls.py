@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import oracle as orc
+from sig_cases import spans
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +56,7 @@ def _batch(pset, keys, n_ops, seed, modes=(0,)):
         kind = i % 6
         if kind in (1, 2, 3):
             b = bytearray(sig)
-            lo, hi = {1: (0, p.ctilde_len), 2: (p.ctilde_len, p.sig_len - p.omega - p.k), 3: (p.sig_len - p.omega - p.k, p.sig_len)}[kind]
+            lo, hi = spans(p)[kind - 1]
             b[int(rng.integers(lo, hi))] ^= 1 << int(rng.integers(0, 8))
             sig = bytes(b)
         elif kind == 4 and mlen:

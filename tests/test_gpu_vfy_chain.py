@@ -4,10 +4,11 @@ way the call must behave as one item of the caller's stream: behind what the str
 after the other.  257 ops over 5 keys per parameter set, every 7th signature damaged (in c~, in z, in the hint section, in turn), at 1,
 64, 65 and 257 ops, against mldsa_verify on the same inputs and the oracle op for op.  The layer is called directly, so the routing
 threshold does not apply; every call is a few hundred ops at most."""
-from fips204_amd import _lib, _vfy_lib
-from fips204_amd.hotpath import _optr, _ptr, _stream
-from fips204_amd.ml_dsa import MODE_PURE, _cat_with_offsets
+from fips204_amd import _vfy_lib
+from fips204_amd.ml_dsa import MODE_PURE
 from gpu_common import *
+from sig_cases import spans
+from vfy_calls import core_verify, fresh, signed_batch, verdicts, vfy_verify
 
 pytestmark = pytest.mark.gpu
 
@@ -17,21 +18,13 @@ FIRST_BAD = 3  # ops 3, 10, 17, ... are damaged: op 0 is good, so a call of one 
 
 
 # ------------------------------------------------------------------------------------------------- the damaged batch, on the CPU
-def sections(gamma1, l, ctilde_len):
-    """(first byte of z, first byte of the hint section) of sigEncode: c~ | z | hints"""
-    cb = 18 if gamma1 == (1 << 17) else 20
-    return ctilde_len, ctilde_len + l * 32 * cb
-
-
-def damaged_batch(sig, gamma1, l, ctilde_len):
+def damaged_batch(p, sig):
     """(a copy of the signatures [n, sig_len] with every 7th damaged by one flipped bit, the damaged ops): the t-th damage lies in c~, z and
     the hint section in turn, and walks through its section with t"""
-    z0, h0 = sections(gamma1, l, ctilde_len)
-    spans = ((0, z0), (z0, h0), (h0, sig.shape[1]))
     out = sig.copy()
     ops = list(range(FIRST_BAD, sig.shape[0], 7))
     for t, op in enumerate(ops):
-        lo, hi = spans[t % 3]
+        lo, hi = spans(p)[t % 3]
         out[op, lo + (131 * (t // 3)) % (hi - lo)] ^= 1 << (t % 8)
     return out, ops
 
@@ -51,21 +44,9 @@ def vfy():
     return lib
 
 
-def fresh(n):
-    return torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda")
-
-
 def vfy_enqueue(lib, m, b, sigs, ok, n, scratch):
     """the layer's call on torch's current stream, nothing waited for"""
-    _vfy_lib.check(lib.mldsa_vfy_verify(m.hp._h, m.pset, MODE_PURE, _ptr(b["pks"].rho), _ptr(b["pks"].tr), _ptr(b["pks"].t1_d2_hat_mont), N_KEYS,
-                                        _ptr(b["kidx"]), _ptr(b["mb"]), _ptr(b["mo"]), None, None, _ptr(sigs), _ptr(ok), n, _ptr(scratch),
-                                        scratch.numel(), _stream(m.device)))
-
-
-def verdicts(ok, n):
-    got = host(ok)[:n]
-    assert set(got.tolist()) <= {0, 1}
-    return got.astype(bool).tolist()
+    vfy_verify(lib, m, b["pks"], b["mb"], b["mo"], sigs, ok, n, kidx=b["kidx"], scratch=scratch)
 
 
 _batches = {}
@@ -76,18 +57,11 @@ def batch(m):
     op for op and the core's at every size of SIZES (and at 200 ops, the several-parts case)."""
     if m.pset in _batches:
         return _batches[m.pset]
-    p = m.params
-    xi = [shake(b"chain-key%d" % m.pset, i) for i in range(N_KEYS)]
-    pk, sk = m.keygen_from_seed(xi)
-    pks, sks = m.public_keys_from_bytes(pk), m.private_keys_from_bytes(sk)
-    msgs = [shake(b"chain-msg%d" % m.pset, i, (0, 1, 33, 70, 135, 136, 300)[i % 7]) for i in range(N_OPS)]
-    rnd = [shake(b"chain-rnd", i) for i in range(N_OPS)]
-    kidx = (np.arange(N_OPS) * 3 % N_KEYS).astype(np.uint32)
-    clean = host(m.try_sign_with_seed(sks, msgs, rnd, key_idx=kidx, mode=MODE_PURE)).copy()
-    bad, ops = damaged_batch(clean, p.gamma1, p.l, p.ctilde_len)
-    mb, mo = _cat_with_offsets(msgs, m.device)
-    okeys = [orc.pk_try_from_bytes(m.pset, host(pk)[i].tobytes()) for i in range(N_KEYS)]
-    b = dict(pks=pks, kidx=kidx_dev(kidx), mb=mb, mo=mo, clean=dev(clean), bad=dev(bad), none=dev(all_damaged(clean)), ops=ops)
+    s = signed_batch(m, b"chain", N_OPS, N_KEYS, lambda i: (0, 1, 33, 70, 135, 136, 300)[i % 7])
+    assert len(s["pks"]) == N_KEYS
+    clean, kidx, msgs, okeys = s["sig"], s["kidx"], s["msgs"], s["okeys"]
+    bad, ops = damaged_batch(m.params, clean)
+    b = dict(pks=s["pks"], kidx=kidx_dev(kidx), mb=s["mb"], mo=s["mo"], clean=dev(clean), bad=dev(bad), none=dev(all_damaged(clean)), ops=ops)
     # ---- the oracle, op for op: the clean signatures pass, the damaged ones are refused and nothing else is
     for name, sg in (("clean", clean), ("bad", bad)):
         b["want_" + name] = [bool(orc.verify_internal(m.pset, okeys[int(kidx[i])], msgs[i], bytes(sg[i]), mode=MODE_PURE)) for i in range(N_OPS)]
@@ -96,10 +70,8 @@ def batch(m):
     # ---- the core on the same inputs, at every size: the same verdicts
     for n in SIZES + (200,):
         for name in ("clean", "bad"):
-            ok = fresh(n)
-            _lib.check(m.lib.mldsa_verify(m.hp._h, m.pset, MODE_PURE, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), N_KEYS, _ptr(b["kidx"]),
-                                          _ptr(mb), _ptr(mo), None, None, _ptr(b[name]), _ptr(ok), n, _stream(m.device)))
-            assert verdicts(ok, n) == b["want_" + name][:n], (n, name)
+            ok = core_verify(m, b["pks"], b["mb"], b["mo"], b[name], fresh(n), n, kidx=b["kidx"])
+            assert verdicts(ok, n).tolist() == b["want_" + name][:n], (n, name)
     _batches[m.pset] = b
     return b
 
@@ -118,7 +90,7 @@ def test_on_the_default_stream_and_on_a_side_stream(vfy, sets, pset, n):
     assert torch.cuda.current_stream() == torch.cuda.default_stream()
     ok = fresh(n)
     vfy_enqueue(vfy, m, b, b["bad"], ok, n, scratch_for(vfy, m, n))
-    assert verdicts(ok, n) == b["want_bad"][:n]
+    assert verdicts(ok, n).tolist() == b["want_bad"][:n]
     side = torch.cuda.Stream()
     ok, scratch = fresh(n), scratch_for(vfy, m, n)
     side.wait_stream(torch.cuda.current_stream())

@@ -4,10 +4,11 @@ Every call is small: the part size is forced to 64 through mldsa_vfy_set_part_op
 import json
 
 import rare_sampler_cases as rc
+import sig_cases
 from fips204_amd import _lib, _vfy_lib
-from fips204_amd.hotpath import _optr, _ptr, _stream
-from fips204_amd.ml_dsa import MODE_PREHASH, MODE_PURE, PublicKeys, _cat_with_offsets
+from fips204_amd.ml_dsa import MODE_PREHASH, MODE_PURE, _cat_with_offsets
 from gpu_common import *
+from vfy_calls import core_verify, gathered, verdicts, vfy_expand_a, vfy_verify
 
 pytestmark = pytest.mark.gpu
 
@@ -27,31 +28,13 @@ def vfy():
     lib.mldsa_vfy_set_part_ops(0)
 
 
-def vfy_verify(lib, m, pks, mb, mo, sigs, ok, n, cb=None, co=None, kidx=None, mode=MODE_PURE, scratch=None):
-    if scratch is None:
-        scratch = filled(lib.mldsa_vfy_scratch_bytes(m.pset, n))
-    _vfy_lib.check(lib.mldsa_vfy_verify(m.hp._h, m.pset, mode, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(kidx),
-                                        _ptr(mb), _ptr(mo), _optr(cb), _optr(co), _ptr(sigs), _ptr(ok), n, _ptr(scratch), scratch.numel(),
-                                        _stream(m.device)))
-    return ok
-
-
-def core_verify(m, pks, mb, mo, sigs, ok, n, cb=None, co=None, kidx=None, mode=MODE_PURE):
-    _lib.check(m.lib.mldsa_verify(m.hp._h, m.pset, mode, _ptr(pks.rho), _ptr(pks.tr), _ptr(pks.t1_d2_hat_mont), len(pks), _optr(kidx), _ptr(mb),
-                                  _ptr(mo), _optr(cb), _optr(co), _ptr(sigs), _ptr(ok), n, _stream(m.device)))
-    return ok
-
-
 def stale(n):
     return torch.full((max(n, 1),), 0x5A, dtype=torch.uint8, device="cuda")
 
 
 def both(lib, m, n, *a, **kw):
     """the verdicts of the library and of the core on the same arguments, as bool arrays"""
-    got = host(vfy_verify(lib, m, *a[:4], stale(n), n, *a[4:], **kw))[:n]
-    ref = host(core_verify(m, *a[:4], stale(n), n, *a[4:], **kw))[:n]
-    assert set(got.tolist()) <= {0, 1} and set(ref.tolist()) <= {0, 1}
-    return got.astype(bool), ref.astype(bool)
+    return verdicts(vfy_verify(lib, m, *a[:4], stale(n), n, *a[4:], **kw), n), verdicts(core_verify(m, *a[:4], stale(n), n, *a[4:], **kw), n)
 
 
 # ------------------------------------------------------------------------------------------------------------- the batch
@@ -98,10 +81,8 @@ def batch(m):
     want = np.ones(N, dtype=bool)
     want[[OP_CTX256, OP_OOR, k]] = False
     okeys = [orc.pk_try_from_bytes(pset, host(pk)[i].tobytes()) for i in range(NK)]
-    gather = torch.from_numpy(kidx.astype(np.int64)).cuda()
     b = dict(pks=pks, sks=sks, okeys=okeys, sig=sig, kidx=kidx, vkidx=vkidx, msgs=msgs, vctx=vctx, want=want, mb=dev(mbuf), mo=dev_off(moff_bad),
-             mo_good=dev_off(moff), cb=dev(cbuf), co=dev_off(coff), moff=moff, moff_bad=moff_bad,
-             per_op=PublicKeys(pset, pks.rho[gather].contiguous(), pks.tr[gather].contiguous(), pks.t1_d2_hat_mont[gather].contiguous()))
+             mo_good=dev_off(moff), cb=dev(cbuf), co=dev_off(coff), moff=moff, moff_bad=moff_bad, per_op=gathered(pks, kidx))
     _batches[pset] = b
     return b
 
@@ -114,14 +95,6 @@ def oracle_verdict(pset, b, i, sig=None):
 
 
 # ---------------------------------------------------------------------------------------------------------- 1: ExpandA seam
-def vfy_expand_a(lib, m, rho):
-    p = m.params
-    n = rho.shape[0]
-    out = torch.full((n, p.k * p.l, 256), -1, dtype=torch.int32, device="cuda")
-    _vfy_lib.check(lib.mldsa_vfy_expand_a(m.hp._h, m.pset, _ptr(rho), _ptr(out), n, _stream(m.device)))
-    return out
-
-
 @pytest.mark.parametrize("n", [1, 2, 3, 13])
 @pytest.mark.parametrize("pset", [44, 65, 87])
 def test_expand_a_seam_is_the_cores_and_the_oracles(vfy, hp, sets, pset, n):
@@ -238,36 +211,13 @@ def damaged(m, good):
     """name -> a damaged copy of the signature `good` (numpy uint8): one flipped bit in c~, in each z polynomial and in the hint section,
     and the three malformed hint shapes"""
     p = m.params
-    cb = 18 if p.gamma1 == (1 << 17) else 20
-    z0, h0 = p.ctilde_len, p.ctilde_len + p.l * 32 * cb
-    out = {}
-
-    def flip(name, byte, bit):
-        s = good.copy()
-        s[byte] ^= 1 << bit
-        out[name] = s
-
-    flip("ctilde_bit", z0 // 2, 3)
-    for j in range(p.l):
-        flip(f"z{j}_bit", z0 + j * 32 * cb + 11 * (j + 1), j % 8)
-    limits = good[h0 + p.omega:h0 + p.omega + p.k].astype(int)
-    total = int(limits[-1])
+    cb, z0, h0 = sig_cases.sections(p)
+    total = int(sig_cases.hint_limits(p, good)[-1])
     assert 2 <= total < p.omega, total  # room for every shape below: positions to swap, padding to dirty
-    flip("hint_bit", h0, 0)  # the first position moves: another w1, or a position that no longer increases
-    starts = np.concatenate([[0], limits[:-1]])
-    i = int(np.argmax(limits - starts))
-    assert limits[i] - starts[i] >= 2
-    s = good.copy()
-    a = h0 + int(starts[i])
-    s[a], s[a + 1] = good[a + 1], good[a]
-    out["hint_positions_not_increasing"] = s
-    s = good.copy()
-    s[h0 + p.omega + p.k - 1] = p.omega + 1
-    out["hint_limit_above_omega"] = s
-    s = good.copy()
-    s[h0 + total] = 1
-    out["hint_padding_not_zero"] = s
-    return out
+    sites = {"ctilde_bit": (z0 // 2, 3), **{f"z{j}_bit": (z0 + j * 32 * cb + 11 * (j + 1), j % 8) for j in range(p.l)},
+             "hint_bit": (h0, 0),  # the first position moves: another w1, or a position that no longer increases
+             "hint_positions_not_increasing": None, "hint_limit_above_omega": None, "hint_padding_not_zero": None}
+    return {name: sig_cases.damage(p, good, name, 0, site) for name, site in sites.items()}
 
 
 @pytest.mark.parametrize("pset", [44, 65, 87])

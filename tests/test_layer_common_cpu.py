@@ -11,8 +11,8 @@ import subprocess
 import pytest
 
 from fips204_amd import _keycheck_lib, _keys_lib, _lib, _mu_lib, _ph_lib, _seed_lib
+from layer_checks import ROOT, sanitized_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fips204_amd")
 LAYER_DIR = os.path.join(PKG, "layer")
 SHARED = [os.path.join(LAYER_DIR, f) for f in ("layer_host.h", "layer_dev.h", "layer.mk", "host_feed.h", "host_chunks.h")]
@@ -185,10 +185,5 @@ def test_one_scaffold_only():
 def test_the_host_feed_under_asan_and_ubsan(tmp_path):
     """layer/host_feed.h, compiled host-only as tests/test_sanitizers_cpu.py compiles the core's host code and linked over the stand-in
     HIP runtime, driven by tests/cpp/host_feed_main.cpp: a stand-alone program, so the sanitizers' runtimes are linked in"""
-    exe = str(tmp_path / "host_feed")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Werror", "-Wno-unused-function", "-x", "hip",
-                           os.path.join(ROOT, "tests", "cpp", "host_feed_main.cpp"), os.path.join(ROOT, "tests", "cpp", "stub_hip_full.cpp"),
-                           "-o", exe])
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert run.returncode == 0 and "host_feed OK" in run.stdout, run.stderr[-2000:]
+    sanitized_program(tmp_path, "host_feed", ["host_feed_main.cpp", "stub_hip_full.cpp"], "host_feed OK", hip_host=True,
+                      env={"ASAN_OPTIONS": "detect_leaks=1"})

@@ -12,7 +12,7 @@ import pytest
 import mus_cases
 from fips204_amd import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _seed_lib
 from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_exports, includes_the_core_device_headers, kernel_resources,
-                          layered_on_core, links_the_core_and_never_builds_it, sources_clean)
+                          layered_on_core, links_the_core_and_never_builds_it, sanitized_program, sources_clean)
 
 MUS_DIR = os.path.join(ROOT, "fips204_amd", "mus")
 SOURCES = ["Makefile", "mus.hip"]
@@ -218,9 +218,4 @@ def test_the_case_generator_covers_what_the_gpu_tests_rely_on(mode):
 
 
 def test_the_chunk_plan_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "mus_chunks")
-    cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "host_chunks_main.cpp")])
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0 and "mus_chunks OK" in run.stdout, run.stderr[-2000:]
+    sanitized_program(tmp_path, "mus_chunks", ["host_chunks_main.cpp"], "mus_chunks OK")

@@ -13,7 +13,7 @@ import rec_cases as rc
 from fips204_amd import _lib, _mus_lib, _rec_lib
 from fips204_amd.ml_dsa import records_blob
 from layer_checks import (PK_SK, ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, kernel_resources, layered_on_core,
-                          links_the_core_and_never_builds_it, sources_clean)
+                          links_the_core_and_never_builds_it, sanitized_program, sources_clean)
 from oracle import oracle as orc
 
 REC_DIR = os.path.join(ROOT, "fips204_amd", "rec")
@@ -280,9 +280,4 @@ def test_refusal_rules_of_the_restatement():
 
 
 def test_the_copy_plan_and_range_check_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "rec_plan")
-    cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "rec_plan_main.cpp")])
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0 and "rec_plan OK" in run.stdout, (run.stdout[-500:], run.stderr[-2000:])
+    sanitized_program(tmp_path, "rec_plan", ["rec_plan_main.cpp"], "rec_plan OK")

@@ -10,7 +10,7 @@ import pytest
 
 from fips204_amd import _lib, _mus_lib, _vfy_lib
 from layer_checks import (KL, ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, includes_the_core_device_headers,
-                          kernel_resources, layered_on_core, links_the_core_and_never_builds_it, scratch_sweep, sources_clean)
+                          kernel_resources, layered_on_core, links_the_core_and_never_builds_it, sanitized_program, scratch_sweep, sources_clean)
 
 VFY_DIR = os.path.join(ROOT, "fips204_amd", "vfy")
 SOURCES = ["Makefile", "vfy.hip", "keccak180.h", "vfy_parts.h"]
@@ -218,9 +218,4 @@ def test_routing_constants():
 
 
 def test_the_part_plan_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "vfy_parts")
-    cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "vfy_parts_main.cpp")])
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0 and "vfy_parts OK" in run.stdout, run.stderr[-2000:]
+    sanitized_program(tmp_path, "vfy_parts", ["vfy_parts_main.cpp"], "vfy_parts OK")

@@ -3,20 +3,14 @@ the lanes as FIFOs and the events as edges, and checks what the plan orders behi
 to back, and that no record or wait of it can go.  enqueue() (vfy.hip) walks the same list, one runtime call per step."""
 import os
 import re
-import subprocess
 
-from layer_checks import ROOT
+from layer_checks import ROOT, sanitized_program
 
 VFY_DIR = os.path.join(ROOT, "fips204_amd", "vfy")
 
 
 def test_the_order_plan_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "vfy_order")
-    cxx = "g++" if subprocess.run(["which", "g++"], capture_output=True).returncode == 0 else "/opt/rocm/lib/llvm/bin/clang++"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror",
-                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "vfy_order_main.cpp")])
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0 and "vfy_order OK" in run.stdout, run.stderr[-4000:]
+    sanitized_program(tmp_path, "vfy_order", ["vfy_order_main.cpp"], "vfy_order OK")
 
 
 def test_enqueue_issues_the_plan_and_nothing_beside_it():
