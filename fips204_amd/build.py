@@ -4,7 +4,9 @@ library fips204_amd/keys/libmldsa_keys.so (include/mldsa_keys.h), the external-m
 (include/mldsa_mu.h), the seed-form key library fips204_amd/seed/libmldsa_seed.so (include/mldsa_seed.h), the strict private-key
 import library fips204_amd/keycheck/libmldsa_keycheck.so (include/mldsa_keycheck.h), the mu-stream library
 fips204_amd/mus/libmldsa_mus.so (include/mldsa_mus.h), the wire-record library fips204_amd/rec/libmldsa_rec.so (include/mldsa_rec.h)
-and the large-batch verify library fips204_amd/vfy/libmldsa_vfy.so (include/mldsa_vfy.h)."""
+and the large-batch verify library fips204_amd/vfy/libmldsa_vfy.so (include/mldsa_vfy.h).  Behind them the front layers, built
+the same way: the request-signing library fips204_amd/recsign/libmldsa_recsign.so (include/mldsa_recsign.h), whose plan header
+includes the wire-record library's (fips204_amd/rec/rec_plan.h)."""
 import os
 import subprocess
 
@@ -14,8 +16,10 @@ LIB = os.path.join(CSRC, "libmldsa_hip.so")
 # the layered libraries in build order: directory under fips204_amd/ -> library file name
 LAYERS = {"ph": "libmldsa_ph.so", "keys": "libmldsa_keys.so", "mu": "libmldsa_mu.so", "seed": "libmldsa_seed.so",
           "keycheck": "libmldsa_keycheck.so", "mus": "libmldsa_mus.so", "rec": "libmldsa_rec.so", "vfy": "libmldsa_vfy.so"}
-# PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB
-for _name, _file in LAYERS.items():
+# built after LAYERS by the same loop
+FRONT_LAYERS = {"recsign": "libmldsa_recsign.so"}
+# PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB, RECSIGN_DIR, RECSIGN_LIB
+for _name, _file in {**LAYERS, **FRONT_LAYERS}.items():
     globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)
     globals()[f"{_name.upper()}_LIB"] = os.path.join(_HERE, _name, _file)
 
@@ -27,7 +31,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for name, file in LAYERS.items():
+    for name, file in {**LAYERS, **FRONT_LAYERS}.items():
         layer_dir = os.path.join(_HERE, name)
         layer_lib = os.path.join(layer_dir, file)
         if force:

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _seed_lib, _vfy_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -1510,3 +1510,176 @@ class MlDsaRecords:
                 ok[torch.from_numpy(mine).to(self.device)] = k["ok"][torch.from_numpy((cs[mine] & 0x3FFFFFFF).astype(np.int64)).to(self.device)]
         torch.cuda.synchronize(self.device)
         return ok.cpu().numpy().astype(bool)
+
+
+# ---- signing of request records (include/mldsa_recsign.h) ---------------------------------------------------------------------------
+def sign_requests_blob(requests, pad=0, front=0, fill=0xC3, in_place=False):
+    """Lays signing requests (pset, key, message, ctx, rnd or None) out in one buffer, field after field -- message, context, the 32
+    bytes of rnd where there are any, and with in_place the hole the signature goes to --, and describes them: (blob, ops, out_len) =
+    (uint8 numpy array, numpy array of _recsign_lib.OP_DTYPE, one mldsa_recsign_op per request, the length of the output buffer).
+    key: the row of the parameter set's key table.  rnd None: the deterministic variant (no MLDSA_RECSIGN_RND flag).
+    pad: the gap in front of every field and every hole, one int or a sequence that is cycled through, so that a caller chooses every
+    field's alignment; front: bytes in front of the first gap; gaps and holes hold `fill`.  Without in_place the holes lie in a
+    separate output buffer, laid out with the same gaps; with it they lie in the blob itself (out_len = the blob's length)."""
+    pads = [int(pad)] if np.isscalar(pad) else [int(x) for x in pad]
+    ops = np.zeros(len(requests), dtype=_recsign_lib.OP_DTYPE)
+    parts, at, k, out_at = [bytes([fill]) * front], front, 0, front
+    for i, (pset, key, message, ctx, rnd) in enumerate(requests):
+        if pset not in _recsign_lib.CLASS_SETS:
+            raise ValueError("sign_requests_blob: unknown parameter set")
+        if len(ctx) > 0xFFFF or len(message) > 0xFFFFFFFF or (rnd is not None and len(rnd) != 32):
+            raise ValueError("sign_requests_blob: a context or message too long for its descriptor field, or rnd not 32 bytes")
+        sig_len = _lib.get_params(pset).sig_len
+        ops[i]["set"], ops[i]["key"], ops[i]["msg_len"], ops[i]["ctx_len"] = pset, key, len(message), len(ctx)
+        ops[i]["flags"] = 0 if rnd is None else _recsign_lib.FLAG_RND
+        fields = [("msg_off", message), ("ctx_off", ctx)] + ([("rnd_off", rnd)] if rnd is not None else [])
+        if in_place:
+            fields.append(("sig_off", bytes([fill]) * sig_len))
+        for name, field in fields:
+            gap = pads[k % len(pads)]
+            k += 1
+            parts += [bytes([fill]) * gap, bytes(field)]
+            ops[i][name] = at + gap
+            at += gap + len(field)
+        if not in_place:
+            gap = pads[k % len(pads)]
+            k += 1
+            ops[i]["sig_off"] = out_at + gap
+            out_at += gap + sig_len
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), ops, (at if in_place else out_at)
+
+
+class MlDsaRecordSigner:
+    """Batched signing straight from serialized requests on one GPU, any mix of parameter sets in one call, every signature written to
+    its byte offset: libmldsa_recsign.so (include/mldsa_recsign.h).  blob, out = uint8 CUDA tensors (any alignment: a slice will do;
+    out may be the blob), ops = uint8 CUDA tensor holding n_ops mldsa_recsign_op descriptors (ops_tensor() uploads a numpy array of
+    _recsign_lib.OP_DTYPE), status = int32 CUDA tensor [n_ops].  The key tables are set_keys()'s PrivateKeys, used where they lie."""
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _recsign_lib.load()
+        self._keys = {}
+
+    def set_keys(self, pset, sks):
+        """the key table of one parameter set: a PrivateKeys (kept by reference, never copied); None: the set is no longer served"""
+        if pset not in _recsign_lib.CLASS_SETS or (sks is not None and sks.pset != pset):
+            raise ValueError("set_keys: the keys of ML-DSA-%s expected" % pset)
+        if sks is None:
+            self._keys.pop(pset, None)
+        else:
+            self._keys[pset] = sks
+
+    def _n_keys(self):
+        return (C.c_size_t * 3)(*[len(self._keys[p]) if p in self._keys else 0 for p in _recsign_lib.CLASS_SETS])
+
+    def _key_tables(self):
+        t = (_recsign_lib.RecsignKeys * 3)()
+        for c, pset in enumerate(_recsign_lib.CLASS_SETS):
+            if pset in self._keys:
+                sks = self._keys[pset]
+                ptrs = [p.value if isinstance(p, C.c_void_p) else p for p in _sk_ptrs(sks)]
+                t[c].n_keys = len(sks)
+                t[c].rho, t[c].cap_k, t[c].tr, t[c].s_1_hat_mont, t[c].s_2_hat_mont, t[c].t_0_hat_mont = ptrs
+        return t
+
+    def ops_tensor(self, ops):
+        a = np.ascontiguousarray(ops, dtype=_recsign_lib.OP_DTYPE)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(48, np.uint8)).to(self.device)
+
+    @staticmethod
+    def _n_ops(ops, n_ops):
+        if ops.dtype != torch.uint8 or ops.numel() % 48:
+            raise ValueError("ops: a uint8 tensor of n_ops * 48 bytes expected")
+        return ops.numel() // 48 if n_ops is None else int(n_ops)
+
+    def plan_device(self, ops, blob_len, out_len, n_ops=None):
+        """mldsa_recsign_plan, asynchronous on the current stream: (class_slot int32 [n_ops] -- (class << 30) | slot, to be read as
+        uint32 --, totals int64 [10] -- ops per class 44 / 65 / 87 / refused, message bytes per class, context bytes per class --,
+        plan uint8: the working memory pack_device takes)."""
+        n = self._n_ops(ops, n_ops)
+        class_slot = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        totals = torch.zeros(10, dtype=torch.int64, device=self.device)
+        plan = torch.empty(max(self.lib.mldsa_recsign_plan_bytes(n), 256), dtype=torch.uint8, device=self.device)
+        _recsign_lib.check(self.lib.mldsa_recsign_plan(self.hp._h, int(blob_len), int(out_len), _ptr(ops), n, self._n_keys(), _ptr(class_slot),
+                                                       _ptr(totals), _ptr(plan), plan.numel(), _stream(self.device)))
+        return class_slot[:n], totals, plan
+
+    def pack_device(self, blob, ops, out_len, class_slot, totals, plan, n_ops=None, arena=None):
+        """mldsa_recsign_pack behind plan_device: waits for the current stream to read the totals (unless `totals` is already a
+        _recsign_lib.RecsignTotals), then packs asynchronously.  Returns {pset: dict(n, key_idx [n], msgs, msg_off [n + 1], ctxs,
+        ctx_off [n + 1], rnd [n, 32], sigs [n, SIG_LEN], status [n])}, every tensor a view of one arena -- what sign_device of
+        MlDsa(pset) takes --, and under "raw" the mldsa_recsign_packed scatter_device takes, under "arena" the arena and under
+        "rnd_region" the view of all rnd rows, which the caller zeroes after signing."""
+        n = self._n_ops(ops, n_ops)
+        if not isinstance(totals, _recsign_lib.RecsignTotals):
+            torch.cuda.current_stream(self.device).synchronize()
+            h = [int(x) for x in totals.cpu().tolist()]
+            totals = _recsign_lib.RecsignTotals()
+            totals.n[:], totals.msg_bytes[:], totals.ctx_bytes[:] = h[0:4], h[4:7], h[7:10]
+        need = self.lib.mldsa_recsign_arena_bytes(totals.n[0], totals.n[1], totals.n[2], sum(totals.msg_bytes), sum(totals.ctx_bytes))
+        if arena is None:
+            arena = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        out = _recsign_lib.RecsignPacked()
+        _recsign_lib.check(self.lib.mldsa_recsign_pack(self.hp._h, _ptr(blob), blob.numel(), int(out_len), _ptr(ops), n, self._n_keys(),
+                                                       _ptr(class_slot), _ptr(plan), plan.numel(), C.byref(totals), _ptr(arena), arena.numel(),
+                                                       C.byref(out), _stream(self.device)))
+        base = arena.data_ptr()
+        cut = lambda p, nbytes: arena[(p or base) - base:(p or base) - base + nbytes]  # noqa: E731
+        packed = dict(raw=out, arena=arena, rnd_region=cut(out.rnd_region, out.rnd_region_bytes))
+        for c, pset in enumerate(_recsign_lib.CLASS_SETS):
+            k, sig_len = out.c[c], _lib.get_params(pset).sig_len
+            packed[pset] = dict(
+                n=int(k.n), key_idx=cut(k.key_idx, 4 * k.n).view(torch.int32), msgs=cut(k.msgs, max(int(totals.msg_bytes[c]), 1)),
+                msg_off=cut(k.msg_off, 8 * (k.n + 1)).view(torch.int64), ctxs=cut(k.ctxs, max(int(totals.ctx_bytes[c]), 1)),
+                ctx_off=cut(k.ctx_off, 8 * (k.n + 1)).view(torch.int64), rnd=cut(k.rnd, 32 * k.n).view(int(k.n), 32),
+                sigs=cut(k.sigs, k.n * sig_len).view(int(k.n), sig_len), status=cut(k.status, 4 * k.n).view(torch.int32))
+        return packed
+
+    def scatter_device(self, ops, blob_len, out, class_slot, packed, status, n_ops=None):
+        """mldsa_recsign_scatter behind the signing calls on the current stream: every accepted op's row of its class's sigs to its
+        offset in `out`, status[i] = the class's status[slot] or the refusal's code.  packed: what pack_device returned."""
+        n = self._n_ops(ops, n_ops)
+        _recsign_lib.check(self.lib.mldsa_recsign_scatter(self.hp._h, _ptr(ops), n, int(blob_len), _ptr(out), out.numel(), self._n_keys(),
+                                                          _ptr(class_slot), C.byref(packed["raw"]), _ptr(status), _stream(self.device)))
+        return out
+
+    def sign_scratch(self, n_ops, msg_bytes, ctx_bytes):
+        """device scratch that no sign_device call of up to n_ops ops with these byte totals can outgrow, whatever its mix"""
+        nb = self.lib.mldsa_recsign_front_bytes(n_ops) + self.lib.mldsa_recsign_arena_bytes_max(n_ops, msg_bytes, ctx_bytes)
+        return torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+
+    def sign_device(self, blob, ops, out, status, n_ops=None, mode=MODE_PURE, scratch=None, info=None):
+        """mldsa_recsign_sign: request i signed under its own parameter set with key `key` of that set's table, the signature written
+        to out[sig_off:], status[i] = mldsa_sign's status or the refusal's code.  Complete when it returns.  scratch: a uint8 tensor,
+        e.g. from sign_scratch(); None: one that holds any mix whose messages and contexts fit the blob four times over (a call that
+        needs more raises MldsaError with MLDSA_ERR_NOMEM, and info names the need).  info: a dict that receives n44, n65, n87,
+        refused, msg_bytes, ctx_bytes and scratch_needed."""
+        n = self._n_ops(ops, n_ops)
+        if scratch is None:
+            scratch = self.sign_scratch(n, 4 * blob.numel(), 4 * blob.numel())
+        got = _recsign_lib.RecsignInfo()
+        rc = self.lib.mldsa_recsign_sign(self.hp._h, mode, self._key_tables(), _ptr(blob), blob.numel(), _ptr(ops), n, _ptr(out), out.numel(),
+                                         _ptr(status), _ptr(scratch), scratch.numel(), C.byref(got), _stream(self.device))
+        if info is not None and rc in (_lib.OK, _lib.ERR_NOMEM) and n:
+            info.update(n44=int(got.n[0]), n65=int(got.n[1]), n87=int(got.n[2]), refused=int(got.n[3]), msg_bytes=int(got.msg_bytes),
+                        ctx_bytes=int(got.ctx_bytes), scratch_needed=int(got.scratch_needed))
+        _recsign_lib.check(rc)
+        return out
+
+    def sign(self, requests, mode=MODE_PURE, in_place=False):
+        """A host list of (pset, key, message, ctx, rnd or None) -> (signatures, status): the requests are laid out in one blob
+        (sign_requests_blob; with in_place the signatures are written into the blob itself) and signed from it.  signatures: a list of
+        bytes, one per request (its hole as it was laid out for a request whose status is not 0); status: an int32 array."""
+        n = len(requests)
+        if n == 0:
+            return [], np.zeros(0, dtype=np.int32)
+        blob_h, ops_h, out_len = sign_requests_blob(requests, in_place=in_place)
+        blob = torch.from_numpy(blob_h.copy() if blob_h.size else np.zeros(1, np.uint8)).to(self.device)[:blob_h.size]
+        out = blob if in_place else torch.zeros(max(out_len, 1), dtype=torch.uint8, device=self.device)[:out_len]
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.sign_device(blob, self.ops_tensor(ops_h), out, status, n, mode)
+        torch.cuda.synchronize(self.device)
+        out_h = out.cpu().numpy()
+        sigs = [out_h[int(o["sig_off"]):int(o["sig_off"]) + _lib.get_params(int(o["set"])).sig_len].tobytes() for o in ops_h]
+        return sigs, status.cpu().numpy()
