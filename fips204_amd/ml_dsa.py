@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -1683,3 +1683,85 @@ class MlDsaRecordSigner:
         out_h = out.cpu().numpy()
         sigs = [out_h[int(o["sig_off"]):int(o["sig_off"]) + _lib.get_params(int(o["set"])).sig_len].tobytes() for o in ops_h]
         return sigs, status.cpu().numpy()
+
+
+# ---- certificate signatures from DER (include/mldsa_x509.h) --------------------------------------------------------------------------
+def certificates_blob(ders, issuers, pad=0, front=0, fill=0xC3):
+    """Lays DER certificates out in one buffer and describes them: (blob, certs) = (uint8 numpy array, numpy array of
+    _x509_lib.CERT_DTYPE, one mldsa_x509_cert per certificate).  issuers[i]: the index of the certificate whose subject key signs
+    certificate i (a self-signed root names itself), or None / _x509_lib.NO_ISSUER for a certificate that is parsed only.
+    pad: the gap in front of every certificate, one int or a sequence that is cycled through, as in records_blob; front: bytes in
+    front of the first gap; the gaps hold `fill`."""
+    if len(ders) != len(issuers):
+        raise ValueError("certificates_blob: one issuer per certificate expected")
+    pads = [int(pad)] if np.isscalar(pad) else [int(x) for x in pad]
+    certs = np.zeros(len(ders), dtype=_x509_lib.CERT_DTYPE)
+    parts, at = [bytes([fill]) * front], front
+    for i, (der, issuer) in enumerate(zip(ders, issuers)):
+        if len(der) > 0xFFFFFFFF:
+            raise ValueError("certificates_blob: a certificate too long for its descriptor field")
+        gap = pads[i % len(pads)]
+        parts += [bytes([fill]) * gap, bytes(der)]
+        certs[i]["off"], certs[i]["len"] = at + gap, len(der)
+        certs[i]["issuer"] = _x509_lib.NO_ISSUER if issuer is None else int(issuer)
+        at += gap + len(der)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), certs
+
+
+class MlDsaCertificates:
+    """The signature leg of X.509 path validation on one GPU, any mix of parameter sets in one call: libmldsa_x509.so
+    (include/mldsa_x509.h) in front of libmldsa_rec.so.  blob = uint8 CUDA tensor (any alignment: a slice will do), certs = uint8 CUDA
+    tensor holding n mldsa_x509_cert entries (certs_tensor() uploads a numpy array of _x509_lib.CERT_DTYPE).  Validity dates, extensions
+    and revocation are not looked at."""
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _x509_lib.load()
+        self.records = MlDsaRecords(hotpath=self.hp)
+
+    def certs_tensor(self, certs):
+        a = np.ascontiguousarray(certs, dtype=_x509_lib.CERT_DTYPE)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(16, np.uint8)).to(self.device)
+
+    @staticmethod
+    def _n(certs, n):
+        if certs.dtype != torch.uint8 or certs.numel() % 16:
+            raise ValueError("certs: a uint8 tensor of n * 16 bytes expected")
+        return certs.numel() // 16 if n is None else int(n)
+
+    def ops_device(self, blob, certs, n=None, check_names=True, status=None):
+        """mldsa_x509_ops, asynchronous on the current stream: (ops uint8 [n * 40] -- one mldsa_rec_op per certificate, all zero
+        where status is not 0, as MlDsaRecords takes them --, status uint8 [n], fields uint8 [n * 56] -- to be read as
+        _x509_lib.FIELDS_DTYPE).  status: a uint8 tensor to write to instead of a new one."""
+        n = self._n(certs, n)
+        ops = torch.empty(max(n, 1) * 40, dtype=torch.uint8, device=self.device)
+        fields = torch.empty(max(n, 1) * 56, dtype=torch.uint8, device=self.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        _x509_lib.check(self.lib.mldsa_x509_ops(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), n, _x509_lib.CHECK_NAMES if check_names else 0,
+                                                _ptr(fields), _ptr(ops), _ptr(status), _stream(self.device)))
+        return ops[:n * 40], status[:n], fields[:n * 56]
+
+    def verify_device(self, blob, certs, ok, status=None, check_names=True, scratch=None):
+        """ok[i] = 1 where certificate i's signature verifies under its issuer's subject key (pure ML-DSA, empty context) and its
+        status is 0; 0 everywhere else.  ops_device, then MlDsaRecords.verify_device on the ops and the same stream (which waits for
+        the stream once).  Returns the status tensor."""
+        n = self._n(certs, None)
+        ops, status, _ = self.ops_device(blob, certs, n, check_names, status=status)
+        if n:
+            self.records.verify_device(blob, ops, ok, n, MODE_PURE, scratch=scratch)
+        return status
+
+    def verify(self, ders, issuers, check_names=True, pad=0):
+        """Host lists of DER certificates and their issuers' indices -> (bool array, status array): the certificates are laid out
+        in one blob (certificates_blob) and verified from it."""
+        n = len(ders)
+        if n == 0:
+            return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.uint8)
+        blob_h, certs_h = certificates_blob(ders, issuers, pad=pad)
+        blob = torch.from_numpy(blob_h.copy() if blob_h.size else np.zeros(1, np.uint8)).to(self.device)[:blob_h.size]
+        ok = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        status = self.verify_device(blob, self.certs_tensor(certs_h), ok, check_names=check_names)
+        torch.cuda.synchronize(self.device)
+        return ok.cpu().numpy().astype(bool), status.cpu().numpy()
