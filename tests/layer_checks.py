@@ -196,6 +196,45 @@ def sources_clean(layer_dir, extra_files, asm_free=True):
     return read
 
 
+def shared_plan_is_shared_once(src, scan, host, makefile, scan_h, host_h):
+    """The record libraries' plan (fips204_amd/rec/rec_scan.h, rec_host.h) is used by the library's .hip `src`, not restated in it:
+    `src` includes both headers under the names `scan_h` and `host_h`, its Makefile names them, the scan's LDS and every shared
+    definition are in the headers alone, and the headers give everything internal linkage."""
+    for h in (scan_h, host_h):
+        assert f'#include "{h}"' in src and h in makefile, h  # a change of a shared header rebuilds the library
+    # LDS: the per-wave partial sums of the two scan kernels only
+    assert scan.count("__shared__") == 2 and "__shared__" not in src + host and "extern __shared__" not in scan
+    for name in ("op_values", "wave_inclusive", "copy_field", "k_classify", "k_offsets", "k_apply", "plan_layout", "front_layout",
+                 "check_plan_memory", "launch_plan", "totals_consistent", "read_totals"):
+        defined = r"^[^\n;=/]*\b(void|bool|int|uint64_t|size_t)\s+%s\s*\(" % name
+        assert not re.search(defined, src, flags=re.M), name
+        assert len(re.findall(defined, scan + host, flags=re.M)) == 1, name
+    for word in ("SCAN_WAVES =", "SLOT_MASK =", "struct PlanLayout", "struct FrontLayout"):
+        assert word not in src and (scan + host).count(word) == 1, word
+    for text in (scan, host):  # layer_host.h's style: two libraries in one process share no kernel stub and no function
+        assert re.search(r"\nnamespace mldsa_rec \{\nnamespace \{\n", text) and text.rstrip().endswith("}  // namespace\n}  // namespace mldsa_rec")
+        assert not re.search(r"\bextern\b", text)
+    assert "__global__" not in host and "hipLaunchKernelGGL" not in scan  # device code in one header, host code in the other
+
+
+# what libmldsa_rec.so and libmldsa_recsign.so exported beside their entry points before the plan was shared: libstdc++'s inline functions
+STD_WEAK = {"_ZNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEC2IS3_EEPKcRKS3_", "_ZNSt7__cxx119to_stringEm",
+            "_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEOS8_PKS5_",
+            "_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEOS8_S9_"}
+
+
+def no_new_dynamic_symbol(lib_path, prefix):
+    """The shared plan adds nothing to the library's dynamic symbol table: a kernel template with external linkage would put a weak host
+    stub of one name into both record libraries, and the loader would bind both to the first."""
+    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], check=True, capture_output=True, text=True).stdout
+    for ln in out.splitlines():
+        kind, name = ln.split()[-2:]
+        if kind in "WwVv":
+            for word in ("k_classify", "k_offsets", "k_apply", "k_pack", "k_scatter", "copy_field", "mldsa_rec", "_GLOBAL__N"):
+                assert word not in name, ln
+        assert (kind == "T" and name.startswith(prefix)) or name in STD_WEAK or re.fullmatch(r"__hip_cuid_[0-9a-f]+", name), ln
+
+
 def includes_the_core_device_headers(layer_dir, source):
     """the core's device headers are included, never copied: through the layers' shared device header, both links of the chain"""
     src = open(os.path.join(layer_dir, source)).read()

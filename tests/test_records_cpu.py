@@ -13,11 +13,12 @@ import rec_cases as rc
 from fips204_amd import _lib, _mus_lib, _rec_lib
 from fips204_amd.ml_dsa import records_blob
 from layer_checks import (PK_SK, ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, kernel_resources, layered_on_core,
-                          links_the_core_and_never_builds_it, sanitized_program, sources_clean)
+                          links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program, shared_plan_is_shared_once,
+                          sources_clean)
 from oracle import oracle as orc
 
 REC_DIR = os.path.join(ROOT, "fips204_amd", "rec")
-SOURCES = ["Makefile", "rec.hip", "rec_plan.h"]
+SOURCES = ["Makefile", "rec.hip", "rec_plan.h", "rec_scan.h", "rec_host.h"]
 
 
 @pytest.fixture(scope="module")
@@ -188,21 +189,29 @@ def test_kernels_do_not_spill_and_sources_are_clean(rec):
     for stem in ("k_classify", "k_offsets", "k_apply", "k_pack", "k_scatter"):
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) == 5
+    # sources_clean reads the whole directory: rec_scan.h and rec_host.h, which libmldsa_recsign.so shares, are among its files
     read = dict(sources_clean(REC_DIR, ["../../include/mldsa_rec.h", "../_rec_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]))
-    src, plan = read["rec.hip"], read["rec_plan.h"]
-    for h in ("../layer/layer_host.h", "../../include/mldsa_rec.h", "rec_plan.h"):
+    src, plan, scan, host = read["rec.hip"], read["rec_plan.h"], read["rec_scan.h"], read["rec_host.h"]
+    for h in ("../layer/layer_host.h", "../../include/mldsa_rec.h", "rec_plan.h", "rec_scan.h", "rec_host.h"):
         assert f'#include "{h}"' in src, h
     # the kernel boundaries do the ordering: no atomics, no flag another workgroup waits for, no spin loop; the scaffold is shared, not copied
     for word in ("atomic", "__threadfence", "while (true)", "for (;;)", "s_sleep", "hipGraph", "hipStreamCreate", "struct DeviceScope",
                  "thread_local", "int fail("):
-        assert word not in src and word not in plan, word
+        assert word not in src + plan + scan + host, word
+    shared_plan_is_shared_once(src, scan, host, open(os.path.join(REC_DIR, "Makefile")).read(), "rec_scan.h", "rec_host.h")
+    no_new_dynamic_symbol(_rec_lib.LIB_PATH, "mldsa_rec_")
     # the plan has no HIP in it, and the kernel keeps no second copy of its arithmetic: it calls the plan's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
-    kernel_code = re.sub(r"//[^\n]*", "", src)
+    own_code = re.sub(r"//[^\n]*", "", src)
+    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan)
     for call in ("copy_plan(", "chunk_src(", "funnel16(", "classify(", "in_range("):
         assert call in kernel_code and "constexpr" in plan, call
-    assert kernel_code.count("mldsa_verify_pk(") == 1 and "hipStreamSynchronize(" in kernel_code and kernel_code.count("hipStreamSynchronize(") == 1
+    for name in ("copy_plan", "chunk_src", "funnel16", "funnel_at", "in_range", "sig_len", "class_of_set", "up256"):
+        assert not re.search(r"constexpr[^;{]*\b%s\s*\(" % name, kernel_code + re.sub(r"//[^\n]*", "", host)), name  # used, not restated
+    assert "classify(" in own_code  # the verdict function is called from the library's own file
+    host_code = own_code + re.sub(r"//[^\n]*", "", host)
+    assert own_code.count("mldsa_verify_pk(") == 1 and host_code.count("hipStreamSynchronize(") == 1
 
 
 # ---- the restatement against the oracle ------------------------------------------------------------------------------------------

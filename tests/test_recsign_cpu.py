@@ -14,7 +14,8 @@ import recsign_cases as rs
 from fips204_amd import _lib, _mus_lib, _recsign_lib
 from fips204_amd.ml_dsa import sign_requests_blob
 from layer_checks import (ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, kernel_resources, layered_on_core,
-                          links_the_core_and_never_builds_it, sanitized_program, sources_clean)
+                          links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program, shared_plan_is_shared_once,
+                          sources_clean)
 from oracle import oracle as orc
 
 RECSIGN_DIR = os.path.join(ROOT, "fips204_amd", "recsign")
@@ -32,14 +33,15 @@ def test_clean_build_in_a_shadow_tree(recsign, tmp_path):
     assert len(build.LAYERS) == 8 and list(build.LAYERS)[-1] == "vfy" and "recsign" not in build.LAYERS
     assert build.FRONT_LAYERS == {"recsign": "libmldsa_recsign.so"}
     assert build.RECSIGN_LIB == _recsign_lib.LIB_PATH and build.RECSIGN_DIR == RECSIGN_DIR
-    # recsign_plan.h includes ../rec/rec_plan.h: the shadow links rec/ too
+    # recsign_plan.h includes ../rec/rec_plan.h and recsign.hip the shared plan (../rec/rec_scan.h, ../rec/rec_host.h): the shadow links rec/ too
     (tmp_path / "fips204_amd").mkdir()
     os.symlink(build.REC_DIR, tmp_path / "fips204_amd" / "rec")
     libs = [os.path.join(build._HERE, d, f) for d, f in {**build.LAYERS, **build.FRONT_LAYERS}.items()]
     clean_build("recsign", _recsign_lib, SOURCES, libs, tmp_path)  # build() builds it: the library is there after build()
     mk = open(os.path.join(RECSIGN_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    assert "../rec/rec_plan.h" in mk  # a change of the shared plan rebuilds this library
+    for h in ("../rec/rec_plan.h", "../rec/rec_scan.h", "../rec/rec_host.h"):
+        assert h in mk, h  # a change of the shared plan rebuilds this library
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "_recsign_lib.load()" in entry  # build() loads the library it built
 
@@ -249,28 +251,34 @@ def test_kernels_do_not_spill_and_sources_are_clean(recsign):
     for stem in ("k_classify", "k_offsets", "k_apply", "k_pack", "k_scatter"):
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) == 5
-    read = dict(sources_clean(RECSIGN_DIR, ["../../include/mldsa_recsign.h", "../_recsign_lib.py", "../layer/layer_host.h", "../rec/rec_plan.h"]))
-    src, plan = read["recsign.hip"], read["recsign_plan.h"]
-    for h in ("../layer/layer_host.h", "../../include/mldsa_recsign.h", "recsign_plan.h"):
+    read = dict(sources_clean(RECSIGN_DIR, ["../../include/mldsa_recsign.h", "../_recsign_lib.py", "../layer/layer_host.h", "../rec/rec_plan.h",
+                                            "../rec/rec_scan.h", "../rec/rec_host.h"]))
+    src, plan, scan, host = read["recsign.hip"], read["recsign_plan.h"], read["../rec/rec_scan.h"], read["../rec/rec_host.h"]
+    for h in ("../layer/layer_host.h", "../../include/mldsa_recsign.h", "recsign_plan.h", "../rec/rec_scan.h", "../rec/rec_host.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../rec/rec_plan.h"' in plan and '#include "rec_plan.h"' not in src and "namespace mldsa_rec " not in src + plan
     # the kernel boundaries do the ordering: no atomics, no flag another workgroup waits for, no spin loop; the scaffold is shared, not copied
     for word in ("atomic", "__threadfence", "while (true)", "for (;;)", "s_sleep", "hipGraph", "hipStreamCreate", "struct DeviceScope",
                  "thread_local", "int fail(", "getenv", "printf"):
-        assert word not in src and word not in plan, word
-    assert not re.search(r"\basm\b", src + plan)
-    assert src.count("__shared__") == 2 and "extern __shared__" not in src  # LDS: the per-wave partial sums of the two scan kernels only
+        assert word not in src + plan + scan + host, word
+    assert not re.search(r"\basm\b", src + plan + scan + host)
+    # LDS (the per-wave partial sums of the two scan kernels only), the definitions and the includes of the shared plan
+    shared_plan_is_shared_once(src, scan, host, open(os.path.join(RECSIGN_DIR, "Makefile")).read(), "../rec/rec_scan.h", "../rec/rec_host.h")
+    no_new_dynamic_symbol(_recsign_lib.LIB_PATH, "mldsa_recsign_")
     # the plan has no HIP in it, and neither file keeps a second copy of the shared arithmetic: they call rec_plan.h's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
-    kernel_code = re.sub(r"//[^\n]*", "", src)
+    own_code = re.sub(r"//[^\n]*", "", src)
+    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan)
     for call in ("copy_plan(", "chunk_src(", "funnel16(", "check_op(", "in_range("):
         assert call in kernel_code and "constexpr" in plan, call
+    host_code = own_code + re.sub(r"//[^\n]*", "", host)
     for name in ("copy_plan", "chunk_src", "funnel16", "funnel_at", "in_range", "sig_len", "class_of_set", "up256"):
-        assert not re.search(r"constexpr[^;{]*\b%s\s*\(" % name, code + kernel_code), name  # used, not restated
+        assert not re.search(r"constexpr[^;{]*\b%s\s*\(" % name, code + kernel_code + host_code), name  # used, not restated
     assert len(re.findall(r"constexpr Verdict check_op\(", code)) == 1 and "in_range(" in code and "sig_len(" in code
-    assert kernel_code.count("mldsa_sign(") == 1 and kernel_code.count("hipStreamSynchronize(") == 1
-    assert "mldsa_memset(" in kernel_code  # the rnd rows are cleared
+    assert "check_op(" in own_code  # the verdict function is called from the library's own file
+    assert own_code.count("mldsa_sign(") == 1 and host_code.count("hipStreamSynchronize(") == 1
+    assert "mldsa_memset(" in own_code  # the rnd rows are cleared
 
 
 # ---- the restatement against the oracle ------------------------------------------------------------------------------------------
