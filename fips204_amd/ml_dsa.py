@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib
+from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -1765,3 +1765,109 @@ class MlDsaCertificates:
         status = self.verify_device(blob, self.certs_tensor(certs_h), ok, check_names=check_names)
         torch.cuda.synchronize(self.device)
         return ok.cpu().numpy().astype(bool), status.cpu().numpy()
+
+
+# ---- certificates issued from TBSCertificates (include/mldsa_x509sign.h) -----------------------------------------------------------------
+def tbs_blob(requests, pad=0, front=0, fill=0xC3):
+    """Lays issuing requests (pset, key_row, tbs_der, rnd or None, issuer) out in one buffer -- each TBSCertificate and, where there is
+    one, its 32 bytes of rnd behind it -- and describes them: (blob, reqs) = (uint8 numpy array, numpy array of
+    _x509sign_lib.REQ_DTYPE, one mldsa_x509sign_req per request).  key_row: the row of the parameter set's key table; rnd None: the
+    deterministic variant (no MLDSA_X509SIGN_RND flag); issuer: copied through to the finished certificate's entry (None:
+    _x509_lib.NO_ISSUER).  pad: the gap in front of every TBS and every rnd, one int or a sequence that is cycled through, as in
+    certificates_blob; front: bytes in front of the first gap; the gaps hold `fill`."""
+    pads = [int(pad)] if np.isscalar(pad) else [int(x) for x in pad]
+    reqs = np.zeros(len(requests), dtype=_x509sign_lib.REQ_DTYPE)
+    parts, at, k = [bytes([fill]) * front], front, 0
+    for i, (pset, key, tbs, rnd, issuer) in enumerate(requests):
+        if len(tbs) > 0xFFFFFFFF or (rnd is not None and len(rnd) != 32) or not 0 <= int(pset) <= 255:
+            raise ValueError("tbs_blob: a TBSCertificate too long for its entry, rnd not 32 bytes, or a set that is no byte")
+        reqs[i]["set"], reqs[i]["key"], reqs[i]["len"] = pset, key, len(tbs)
+        reqs[i]["issuer"] = _x509_lib.NO_ISSUER if issuer is None else int(issuer)
+        reqs[i]["flags"] = 0 if rnd is None else _x509sign_lib.FLAG_RND
+        for name, field in [("off", tbs)] + ([("rnd_off", rnd)] if rnd is not None else []):
+            gap = pads[k % len(pads)]
+            k += 1
+            parts += [bytes([fill]) * gap, bytes(field)]
+            reqs[i][name] = at + gap
+            at += gap + len(field)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), reqs
+
+
+class MlDsaCertificateIssuer:
+    """X.509 certificates issued on one GPU from DER TBSCertificates, any mix of parameter sets in one call: libmldsa_x509sign.so
+    (include/mldsa_x509sign.h) in front of libmldsa_recsign.so.  blob, out = uint8 CUDA tensors (any alignment: a slice will do; they
+    must not overlap), reqs = uint8 CUDA tensor holding n mldsa_x509sign_req entries (requests_tensor() uploads a numpy array of
+    _x509sign_lib.REQ_DTYPE).  The key tables are set_keys()'s PrivateKeys, used where they lie.  Validity dates, extensions and name
+    chaining are not looked at."""
+
+    tbs_blob = staticmethod(tbs_blob)
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _x509sign_lib.load()
+        self.signer = MlDsaRecordSigner(hotpath=self.hp)
+
+    def set_keys(self, pset, sks):
+        """the issuers' key table of one parameter set: a PrivateKeys (kept by reference, never copied); None: the set is not served"""
+        self.signer.set_keys(pset, sks)
+
+    def requests_tensor(self, reqs):
+        a = np.ascontiguousarray(reqs, dtype=_x509sign_lib.REQ_DTYPE)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(32, np.uint8)).to(self.device)
+
+    @staticmethod
+    def _n(reqs, n):
+        if reqs.dtype != torch.uint8 or reqs.numel() % 32:
+            raise ValueError("reqs: a uint8 tensor of n * 32 bytes expected")
+        return reqs.numel() // 32 if n is None else int(n)
+
+    def plan_memory(self, n):
+        return torch.empty(max(self.lib.mldsa_x509sign_plan_bytes(n), 256), dtype=torch.uint8, device=self.device)
+
+    def issue_ops_device(self, blob, reqs, out, n=None, plan=None):
+        """mldsa_x509sign_issue_ops, asynchronous on the current stream: every accepted certificate's frame -- all but its signature
+        -- is written to `out`.  Returns (out_certs uint8 [n * 16] -- one mldsa_x509_cert per request, as MlDsaCertificates takes them
+        with `out` as the blob --, ops uint8 [n * 48] -- one mldsa_recsign_op per request, all zero where status is not 0, as
+        MlDsaRecordSigner takes them --, status uint8 [n], totals int64 [3] -- accepted, refused, out_bytes).  plan: the working memory,
+        a uint8 tensor from plan_memory()."""
+        n = self._n(reqs, n)
+        out_certs = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=self.device)
+        ops = torch.empty(max(n, 1) * 48, dtype=torch.uint8, device=self.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        totals = torch.zeros(3, dtype=torch.int64, device=self.device)
+        if plan is None:
+            plan = self.plan_memory(n)
+        _x509sign_lib.check(self.lib.mldsa_x509sign_issue_ops(self.hp._h, _ptr(blob), blob.numel(), _ptr(reqs), n, self.signer._n_keys(),
+                                                              _ptr(out), out.numel(), _ptr(out_certs), _ptr(ops), _ptr(status), _ptr(totals),
+                                                              _ptr(plan), plan.numel(), _stream(self.device)))
+        return out_certs[:n * 16], ops[:n * 48], status[:n], totals
+
+    def issue_device(self, blob, reqs, out, sig_status, n=None, plan=None, scratch=None):
+        """The two calls: issue_ops_device, then MlDsaRecordSigner.sign_device (pure ML-DSA, empty context) on the ops and the same
+        stream, which writes every accepted certificate's signature into its hole and sig_status[i] (int32 [n]).  Certificate i is
+        issued where status[i] == 0 and sig_status[i] == 0.  Complete when it returns.  Returns (out_certs, status, totals)."""
+        n = self._n(reqs, n)
+        out_certs, ops, status, totals = self.issue_ops_device(blob, reqs, out, n, plan=plan)
+        if n:
+            self.signer.sign_device(blob, ops, out, sig_status, n, MODE_PURE, scratch=scratch)
+        return out_certs, status, totals
+
+    def issue(self, requests, pad=0):
+        """A host list of (pset, key_row, tbs_der, rnd or None, issuer) -> (certificates, status, sig_status): the requests are laid
+        out in one blob (tbs_blob) and issued from it.  certificates: a list of DER bytes, None for a request that was refused or
+        whose signing gave up; status: a uint8 array; sig_status: an int32 array."""
+        n = len(requests)
+        if n == 0:
+            return [], np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int32)
+        blob_h, reqs_h = tbs_blob(requests, pad=pad)
+        out_len = self.lib.mldsa_x509sign_out_bytes_max(n, int(sum(len(r[2]) for r in requests)))
+        blob = torch.from_numpy(blob_h.copy() if blob_h.size else np.zeros(1, np.uint8)).to(self.device)[:blob_h.size]
+        out = torch.zeros(max(out_len, 1), dtype=torch.uint8, device=self.device)
+        sig_status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        out_certs, status, _ = self.issue_device(blob, self.requests_tensor(reqs_h), out, sig_status, n)
+        torch.cuda.synchronize(self.device)
+        out_h, st, sst = out.cpu().numpy(), status.cpu().numpy(), sig_status.cpu().numpy()
+        rows = out_certs.cpu().numpy().view(_x509_lib.CERT_DTYPE)
+        certs = [out_h[int(c["off"]):int(c["off"]) + int(c["len"])].tobytes() if st[i] == 0 and sst[i] == 0 else None for i, c in enumerate(rows)]
+        return certs, st, sst
