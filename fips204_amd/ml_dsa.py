@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
+from . import _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -1868,6 +1868,190 @@ class MlDsaCertificateIssuer:
         out_certs, status, _ = self.issue_device(blob, self.requests_tensor(reqs_h), out, sig_status, n)
         torch.cuda.synchronize(self.device)
         out_h, st, sst = out.cpu().numpy(), status.cpu().numpy(), sig_status.cpu().numpy()
+        rows = out_certs.cpu().numpy().view(_x509_lib.CERT_DTYPE)
+        certs = [out_h[int(c["off"]):int(c["off"]) + int(c["len"])].tobytes() if st[i] == 0 and sst[i] == 0 else None for i, c in enumerate(rows)]
+        return certs, st, sst
+
+
+# ---- certification requests: proof of possession and TBSCertificates (include/mldsa_csr.h) ------------------------------------------------
+def csr_blob(ders, templates=None, pad=0, front=0, fill=0xC3):
+    """Lays DER certification requests out in one buffer and describes them: (blob, items) = (uint8 numpy array, numpy array of
+    _csr_lib.ITEM_DTYPE, one mldsa_csr_item per request).  With templates -- one (pset, key_row, serial, issuer_name, validity,
+    extensions or b"", rnd or None, issuer) per request: the set and the row of the CA key that will sign, the serial number's content
+    bytes, the DER issuer Name, Validity and [3] extensions, and the index copied through to the finished certificate's entry (None:
+    _x509_lib.NO_ISSUER) -- the template pieces are laid out behind the requests, equal pieces once, and (blob, items, entries) is
+    returned with entries a numpy array of _csr_lib.ISSUE_DTYPE.  rnd is not laid out here: it belongs to the buffer the
+    TBSCertificates go to, so entries[i]["rnd_off"] is left 0 and only the flag is set.
+    pad: the gap in front of every request and every piece, one int or a sequence that is cycled through, as in certificates_blob;
+    front: bytes in front of the first gap; the gaps hold `fill`."""
+    pads = [int(pad)] if np.isscalar(pad) else [int(x) for x in pad]
+    items = np.zeros(len(ders), dtype=_csr_lib.ITEM_DTYPE)
+    parts, at, k = [bytes([fill]) * front], front, 0
+
+    def lay(field):
+        nonlocal at, k
+        gap = pads[k % len(pads)]
+        k += 1
+        parts.extend([bytes([fill]) * gap, bytes(field)])
+        at += gap + len(field)
+        return at - len(field)
+
+    for i, der in enumerate(ders):
+        if len(der) > 0xFFFFFFFF:
+            raise ValueError("csr_blob: a request too long for its descriptor field")
+        items[i]["off"], items[i]["len"] = lay(der), len(der)
+    if templates is None:
+        return np.frombuffer(b"".join(parts), dtype=np.uint8), items
+    if len(templates) != len(ders):
+        raise ValueError("csr_blob: one template per request expected")
+    entries = np.zeros(len(ders), dtype=_csr_lib.ISSUE_DTYPE)
+    placed = {}
+    for i, (pset, key, serial, issuer_name, validity, ext, rnd, issuer) in enumerate(templates):
+        if not 0 <= int(pset) <= 255 or len(serial) > 255 or (rnd is not None and len(rnd) != 32):
+            raise ValueError("csr_blob: a set or a serial length that is no byte, or rnd not 32 bytes")
+        e = entries[i]
+        e["set"], e["key"], e["serial_len"], e["flags"] = pset, key, len(serial), 0 if rnd is None else _csr_lib.FLAG_RND
+        e["issuer"] = _x509_lib.NO_ISSUER if issuer is None else int(issuer)
+        for name, piece in (("serial", serial), ("issuer", issuer_name), ("validity", validity), ("ext", ext)):
+            piece = bytes(piece)
+            if piece and piece not in placed:
+                placed[piece] = lay(piece)
+            e[name + "_off"] = placed.get(piece, 0)
+            if name != "serial":
+                e[name + "_len"] = len(piece)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), items, entries
+
+
+class MlDsaCertificateRequests:
+    """PKCS#10 certification requests on one GPU, any mix of parameter sets in one call: libmldsa_csr.so (include/mldsa_csr.h) in front
+    of libmldsa_rec.so (the proof of possession) and of libmldsa_x509sign.so and libmldsa_recsign.so (the certificate).  blob, tbs, out =
+    uint8 CUDA tensors (any alignment: a slice will do; no two may overlap), items / entries = uint8 CUDA tensors holding n
+    mldsa_csr_item / mldsa_csr_issue rows (items_tensor() and issue_tensor() upload numpy arrays of _csr_lib.ITEM_DTYPE and
+    _csr_lib.ISSUE_DTYPE).  The CA's key tables are set_keys()'s PrivateKeys.  Attributes, name policy and validity dates are not
+    looked at."""
+
+    csr_blob = staticmethod(csr_blob)
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _csr_lib.load()
+        self.records = MlDsaRecords(hotpath=self.hp)
+        self.issuer = MlDsaCertificateIssuer(hotpath=self.hp)
+
+    def set_keys(self, pset, sks):
+        """the CA's key table of one parameter set: a PrivateKeys (kept by reference, never copied); None: the set is not served"""
+        self.issuer.set_keys(pset, sks)
+
+    def _rows(self, rows, dtype):
+        a = np.ascontiguousarray(rows, dtype=dtype)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(dtype.itemsize, np.uint8)).to(self.device)
+
+    def items_tensor(self, items):
+        return self._rows(items, _csr_lib.ITEM_DTYPE)
+
+    def issue_tensor(self, entries):
+        return self._rows(entries, _csr_lib.ISSUE_DTYPE)
+
+    @staticmethod
+    def _n(rows, n, size, what):
+        if rows.dtype != torch.uint8 or rows.numel() % size:
+            raise ValueError("%s: a uint8 tensor of n * %d bytes expected" % (what, size))
+        return rows.numel() // size if n is None else int(n)
+
+    def plan_memory(self, n):
+        return torch.empty(max(self.lib.mldsa_csr_plan_bytes(n), 256), dtype=torch.uint8, device=self.device)
+
+    def parse_device(self, blob, items, n=None, status=None):
+        """mldsa_csr_parse, asynchronous on the current stream: (fields uint8 [n * 56] -- to be read as _csr_lib.FIELDS_DTYPE --, ops
+        uint8 [n * 40] -- one mldsa_rec_op per request, all zero where status is not 0, as MlDsaRecords takes them --, status uint8
+        [n]).  status: a uint8 tensor to write to instead of a new one."""
+        n = self._n(items, n, 16, "items")
+        fields = torch.empty(max(n, 1) * 56, dtype=torch.uint8, device=self.device)
+        ops = torch.empty(max(n, 1) * 40, dtype=torch.uint8, device=self.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        _csr_lib.check(self.lib.mldsa_csr_parse(self.hp._h, _ptr(blob), blob.numel(), _ptr(items), n, _ptr(fields), _ptr(ops), _ptr(status),
+                                                _stream(self.device)))
+        return fields[:n * 56], ops[:n * 40], status[:n]
+
+    def verify_device(self, blob, items, ok, n=None, scratch=None):
+        """ok[i] = 1 where request i is well formed and signed by the key it carries (pure ML-DSA, empty context); 0 everywhere else.
+        parse_device, then MlDsaRecords.verify_device on the ops and the same stream (which waits for the stream once).  Returns
+        (fields, status)."""
+        n = self._n(items, n, 16, "items")
+        fields, ops, status = self.parse_device(blob, items, n)
+        if n:
+            self.records.verify_device(blob, ops, ok, n, MODE_PURE, scratch=scratch)
+        return fields, status
+
+    def tbs_device(self, blob, fields, entries, ok, out, n=None, plan=None):
+        """mldsa_csr_tbs, asynchronous on the current stream: the TBSCertificate of every request that is accepted and possessed is
+        written to `out`.  Returns (reqs uint8 [n * 32] -- one mldsa_x509sign_req per request, all zero where status is not 0, as
+        MlDsaCertificateIssuer takes them with `out` as the blob --, status uint8 [n], totals int64 [3] -- accepted, refused,
+        out_bytes).  plan: the working memory, a uint8 tensor from plan_memory()."""
+        n = self._n(entries, n, 64, "entries")
+        reqs = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=self.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        totals = torch.zeros(3, dtype=torch.int64, device=self.device)
+        if plan is None:
+            plan = self.plan_memory(n)
+        _csr_lib.check(self.lib.mldsa_csr_tbs(self.hp._h, _ptr(blob), blob.numel(), _ptr(fields), _ptr(entries), _ptr(ok), n, _ptr(out),
+                                              out.numel(), _ptr(reqs), _ptr(status), _ptr(totals), _ptr(plan), plan.numel(),
+                                              _stream(self.device)))
+        return reqs[:n * 32], status[:n], totals
+
+    def issue_device(self, blob, items, entries, tbs, out, sig_status, n=None, tbs_len=None, scratch=None):
+        """The five calls: parse_device, MlDsaRecords.verify_device, tbs_device into tbs[:tbs_len], then
+        MlDsaCertificateIssuer.issue_device with the whole of `tbs` as its blob -- a caller that signs hedged keeps the randomness in
+        tbs[tbs_len:] and points the entries' rnd_off there.  Request i is a certificate where status[i] == 0, issue_status[i] == 0 and
+        sig_status[i] == 0 (int32 [n]).  Complete when it returns.  Returns (out_certs -- one mldsa_x509_cert per request, as
+        MlDsaCertificates takes them with `out` as the blob --, status, issue_status, totals -- mldsa_csr_tbs's)."""
+        n = self._n(items, n, 16, "items")
+        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        fields, _ = self.verify_device(blob, items, ok, n, scratch=scratch)
+        reqs, status, totals = self.tbs_device(blob, fields, entries, ok, tbs if tbs_len is None else tbs[:tbs_len], n)
+        out_certs, issue_status, _ = self.issuer.issue_device(tbs, reqs, out, sig_status, n)
+        return out_certs, status, issue_status, totals
+
+    def verify(self, ders, pad=0):
+        """A host list of DER certification requests -> (bool array, status array): the requests are laid out in one blob (csr_blob)
+        and their proofs of possession verified from it."""
+        n = len(ders)
+        if n == 0:
+            return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.uint8)
+        blob_h, items_h = csr_blob(ders, pad=pad)
+        blob = torch.from_numpy(blob_h.copy()).to(self.device)
+        ok = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        _, status = self.verify_device(blob, self.items_tensor(items_h), ok, n)
+        torch.cuda.synchronize(self.device)
+        return ok.cpu().numpy().astype(bool), status.cpu().numpy()
+
+    def issue(self, ders, templates, pad=0):
+        """Host lists of DER certification requests and their templates (csr_blob) -> (certificates, status, sig_status).
+        certificates: a list of DER bytes, None for a request that was refused at any stage or whose signing gave up; status: a uint8
+        array, the first nonzero of mldsa_csr_tbs's and mldsa_x509sign_issue_ops's; sig_status: an int32 array."""
+        n = len(ders)
+        if n == 0:
+            return [], np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int32)
+        blob_h, items_h, entries_h = csr_blob(ders, templates, pad=pad)
+        tbs_len = int(sum(len(d) + 64 + len(t[3]) + len(t[4]) + len(t[5]) for d, t in zip(ders, templates)))
+        rnd = np.zeros((n, 32), dtype=np.uint8)
+        for i, t in enumerate(templates):
+            if t[6] is not None:
+                rnd[i] = np.frombuffer(bytes(t[6]), dtype=np.uint8)
+                entries_h[i]["rnd_off"] = tbs_len + 32 * i
+        blob = torch.from_numpy(blob_h.copy()).to(self.device)
+        tbs = torch.zeros(tbs_len + 32 * n, dtype=torch.uint8, device=self.device)
+        tbs[tbs_len:] = torch.from_numpy(rnd.reshape(-1)).to(self.device)
+        out = torch.zeros(self.issuer.lib.mldsa_x509sign_out_bytes_max(n, tbs_len), dtype=torch.uint8, device=self.device)
+        sig_status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        out_certs, status, issue_status, _ = self.issue_device(blob, self.items_tensor(items_h), self.issue_tensor(entries_h), tbs, out,
+                                                               sig_status, n, tbs_len=tbs_len)
+        torch.cuda.synchronize(self.device)
+        tbs[tbs_len:].zero_()  # the randomness of the hedged variant
+        out_h, st, ist, sst = out.cpu().numpy(), status.cpu().numpy(), issue_status.cpu().numpy(), sig_status.cpu().numpy()
+        st = np.where(st != 0, st, ist).astype(np.uint8)
         rows = out_certs.cpu().numpy().view(_x509_lib.CERT_DTYPE)
         certs = [out_h[int(c["off"]):int(c["off"]) + int(c["len"])].tobytes() if st[i] == 0 and sst[i] == 0 else None for i, c in enumerate(rows)]
         return certs, st, sst
