@@ -11,7 +11,8 @@ fips204_amd/x509/libmldsa_x509.so (include/mldsa_x509.h), which writes the wire-
 and the issue layers: the certificate-issuing library fips204_amd/x509sign/libmldsa_x509sign.so (include/mldsa_x509sign.h), which
 writes the request-signing library's descriptors and links the core only, and the request layers: the certification-request library
 fips204_amd/csr/libmldsa_csr.so (include/mldsa_csr.h), which writes the wire-record and the certificate-issuing libraries' descriptors
-and links the core only."""
+and links the core only, and the revocation layers: the revocation-list library fips204_amd/crl/libmldsa_crl.so (include/mldsa_crl.h), which
+writes the wire-record library's descriptors from CRLs, reads the certificate library's rows and links the core only."""
 import os
 import subprocess
 
@@ -29,8 +30,11 @@ PARSE_LAYERS = {"x509": "libmldsa_x509.so"}
 ISSUE_LAYERS = {"x509sign": "libmldsa_x509sign.so"}
 # built after ISSUE_LAYERS by the same loop
 REQUEST_LAYERS = {"csr": "libmldsa_csr.so"}
-# PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB, RECSIGN_DIR, RECSIGN_LIB, X509_DIR, X509_LIB, X509SIGN_DIR, X509SIGN_LIB, CSR_DIR, CSR_LIB
-for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS}.items():
+# built after REQUEST_LAYERS by the same loop
+REVOCATION_LAYERS = {"crl": "libmldsa_crl.so"}
+# PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB, RECSIGN_DIR, RECSIGN_LIB, X509_DIR, X509_LIB, X509SIGN_DIR, X509SIGN_LIB, CSR_DIR, CSR_LIB,
+# CRL_DIR, CRL_LIB
+for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS}.items():
     globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)
     globals()[f"{_name.upper()}_LIB"] = os.path.join(_HERE, _name, _file)
 
@@ -42,7 +46,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS}.items():
+    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS}.items():
         layer_dir = os.path.join(_HERE, name)
         layer_lib = os.path.join(layer_dir, file)
         if force:

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
+from . import _crl_lib, _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -2055,3 +2055,131 @@ class MlDsaCertificateRequests:
         rows = out_certs.cpu().numpy().view(_x509_lib.CERT_DTYPE)
         certs = [out_h[int(c["off"]):int(c["off"]) + int(c["len"])].tobytes() if st[i] == 0 and sst[i] == 0 else None for i, c in enumerate(rows)]
         return certs, st, sst
+
+
+# ---- certificate revocation lists (include/mldsa_crl.h) ------------------------------------------------------------------------------
+def _crl_items(rows):
+    """mldsa_x509_cert rows (offset, length, issuer) as mldsa_crl_item rows: the same three fields"""
+    items = np.zeros(len(rows), dtype=_crl_lib.ITEM_DTYPE)
+    for f in ("off", "len", "issuer"):
+        items[f] = rows[f]
+    return items
+
+
+def crl_blob(crls, issuers, pad=0, front=0, fill=0xC3):
+    """Lays DER CertificateLists out in one buffer and describes them: (blob, items) = (uint8 numpy array, numpy array of
+    _crl_lib.ITEM_DTYPE, one mldsa_crl_item per CRL).  issuers[i]: the row, among the certificates' mldsa_x509_fields, of the CA
+    certificate whose subject key signs CRL i.  pad, front, fill: as in certificates_blob.  The certificates that a lookup reads lie
+    in the same buffer: a caller who needs both lays the CRLs out behind them (front = the bytes in front)."""
+    if len(crls) != len(issuers):
+        raise ValueError("crl_blob: one issuer per CRL expected")
+    blob, rows = certificates_blob(crls, issuers, pad=pad, front=front, fill=fill)
+    return blob, _crl_items(rows)
+
+
+class MlDsaRevocationLists:
+    """The revocation leg of X.509 path validation on one GPU, any mix of parameter sets in one call: libmldsa_crl.so
+    (include/mldsa_crl.h) in front of and behind libmldsa_rec.so, beside libmldsa_x509.so.  blob = uint8 CUDA tensor that holds the
+    CRLs and the certificates (any alignment: a slice will do), items = uint8 CUDA tensor holding n mldsa_crl_item rows
+    (items_tensor() uploads a numpy array of _crl_lib.ITEM_DTYPE).  Update times, delta and indirect CRLs, distribution points and
+    critical extensions are not looked at."""
+
+    crl_blob = staticmethod(crl_blob)
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _crl_lib.load()
+        self.certificates = MlDsaCertificates(hotpath=self.hp)
+        self.records = self.certificates.records
+
+    def items_tensor(self, items):
+        a = np.ascontiguousarray(items, dtype=_crl_lib.ITEM_DTYPE)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(16, np.uint8)).to(self.device)
+
+    @staticmethod
+    def _n(rows, n, size, what):
+        if rows.dtype != torch.uint8 or rows.numel() % size:
+            raise ValueError("%s: a uint8 tensor of n * %d bytes expected" % (what, size))
+        return rows.numel() // size if n is None else int(n)
+
+    def ops_device(self, blob, items, cert_fields, n=None, max_entries=None, check_names=True):
+        """mldsa_crl_ops, asynchronous on the current stream: (ops uint8 [n * 40] -- one mldsa_rec_op per CRL, all zero where status
+        is not 0, as MlDsaRecords takes them --, status uint8 [n], crl_fields uint8 [n * 88] -- to be read as _crl_lib.FIELDS_DTYPE
+        --, entries uint8 [max_entries * 32] -- _crl_lib.ENTRY_DTYPE --, totals int64 [5] -- _crl_lib.TOTALS_DTYPE).  cert_fields:
+        the rows MlDsaCertificates.ops_device returned.  max_entries None: blob.numel() // 20 slots, which CRLs that do not overlap
+        cannot outgrow."""
+        n = self._n(items, n, 16, "items")
+        n_certs = self._n(cert_fields, None, 56, "cert_fields")
+        if max_entries is None:
+            max_entries = blob.numel() // 20
+        entries = torch.empty(max(max_entries, 1) * 32, dtype=torch.uint8, device=self.device)
+        ops = torch.empty(max(n, 1) * 40, dtype=torch.uint8, device=self.device)
+        fields = torch.empty(max(n, 1) * 88, dtype=torch.uint8, device=self.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        totals = torch.zeros(5, dtype=torch.int64, device=self.device)
+        scratch = torch.empty(max(self.lib.mldsa_crl_scratch_bytes(n), 256), dtype=torch.uint8, device=self.device)
+        _crl_lib.check(self.lib.mldsa_crl_ops(self.hp._h, _ptr(blob), blob.numel(), _ptr(items), n, _ptr(cert_fields), n_certs,
+                                              _crl_lib.CHECK_NAMES if check_names else 0, _ptr(fields), _ptr(entries), max_entries, _ptr(ops),
+                                              _ptr(status), _ptr(totals), _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return ops[:n * 40], status[:n], fields[:n * 88], entries[:max_entries * 32], totals
+
+    def table_device(self, entries, totals=None):
+        """mldsa_crl_table, asynchronous on the current stream: (table int32 [mldsa_crl_table_slots], totals) -- the lookup table over
+        the entry rows, built once per CRL refresh and taken by every check_device.  totals: mldsa_crl_ops' row, whose overflow field
+        the call writes; None: a new one."""
+        max_entries = self._n(entries, None, 32, "entries")
+        slots = self.lib.mldsa_crl_table_slots(max_entries)
+        table = torch.empty(slots, dtype=torch.int32, device=self.device)
+        if totals is None:
+            totals = torch.zeros(5, dtype=torch.int64, device=self.device)
+        _crl_lib.check(self.lib.mldsa_crl_table(self.hp._h, _ptr(entries), max_entries, _ptr(table), slots, _ptr(totals), _stream(self.device)))
+        return table, totals
+
+    def check_device(self, blob, certs, cert_fields, cert_crl, items, crl_fields, crl_status, crl_ok, entries, table, revocation=None):
+        """mldsa_crl_check, asynchronous on the current stream: revocation uint8 [n_certs], one of _crl_lib.GOOD ... SCOPE per
+        certificate.  certs, cert_fields: MlDsaCertificates' rows; cert_crl: an int32 CUDA tensor, the CRL that covers each certificate
+        or -1 (MLDSA_CRL_NONE); crl_ok: MlDsaRecords' verdicts on the CRLs' ops, or None."""
+        n_certs = self._n(certs, None, 16, "certs")
+        n_crls = self._n(items, None, 16, "items")
+        if cert_crl.dtype != torch.int32 or cert_crl.numel() < n_certs:
+            raise ValueError("cert_crl: an int32 tensor of n_certs elements expected")
+        if revocation is None:
+            revocation = torch.empty(max(n_certs, 1), dtype=torch.uint8, device=self.device)
+        _crl_lib.check(self.lib.mldsa_crl_check(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), _ptr(cert_fields), _ptr(cert_crl), n_certs,
+                                                _ptr(items), _ptr(crl_fields), _ptr(crl_status), None if crl_ok is None else _ptr(crl_ok), n_crls,
+                                                _ptr(entries), entries.numel() // 32, _ptr(table), table.numel(), _ptr(revocation),
+                                                _stream(self.device)))
+        return revocation[:n_certs]
+
+    def check(self, cert_ders, cert_issuers, crl_ders, crl_issuers, cert_crl, pad=0, check_names=True):
+        """Host lists of DER certificates with their issuers' indices, DER CRLs with the index of the CA certificate that signs each,
+        and for every certificate the index of the CRL that covers it (None: none) -> (revocation, cert_ok, cert_status, crl_ok,
+        crl_status): everything is laid out in one blob, the certificates' and the CRLs' signatures are verified from it
+        (mldsa_x509_ops, mldsa_crl_ops, mldsa_rec_verify on each), the table is built and every certificate looked up."""
+        n_certs, n_crls = len(cert_ders), len(crl_ders)
+        if len(cert_crl) != n_certs:
+            raise ValueError("check: one CRL index (or None) per certificate expected")
+        if n_certs == 0:
+            return (np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=bool), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=bool),
+                    np.zeros(0, dtype=np.uint8))
+        blob_h, rows = certificates_blob(list(cert_ders) + list(crl_ders), list(cert_issuers) + list(crl_issuers), pad=pad)
+        blob = torch.from_numpy(blob_h.copy()).to(self.device)
+        certs, items = self.certificates.certs_tensor(rows[:n_certs]), self.items_tensor(_crl_items(rows[n_certs:]))[:n_crls * 16]
+        covered = np.array([_crl_lib.NONE if c is None else int(c) for c in cert_crl], dtype=np.uint32).view(np.int32)
+        cert_ok = torch.zeros(n_certs, dtype=torch.uint8, device=self.device)
+        crl_ok = torch.zeros(max(n_crls, 1), dtype=torch.uint8, device=self.device)
+        cert_ops, cert_status, cert_fields = self.certificates.ops_device(blob, certs, n_certs, check_names)
+        self.records.verify_device(blob, cert_ops, cert_ok, n_certs, MODE_PURE)
+        max_entries = int(sum(self.lib.mldsa_crl_entries_bound(len(d)) for d in crl_ders))
+        crl_ops, crl_status, crl_fields, entries, totals = self.ops_device(blob, items, cert_fields, n_crls, max_entries, check_names)
+        if n_crls:
+            self.records.verify_device(blob, crl_ops, crl_ok, n_crls, MODE_PURE)
+        table, totals = self.table_device(entries, totals)
+        revocation = self.check_device(blob, certs, cert_fields, torch.from_numpy(covered.copy()).to(self.device), items, crl_fields, crl_status,
+                                       crl_ok, entries, table)
+        torch.cuda.synchronize(self.device)
+        if int(totals.cpu().numpy().view(_crl_lib.TOTALS_DTYPE)[0]["overflow"]):
+            raise RuntimeError("mldsa_crl_table: the lookup table overflowed")
+        return (revocation.cpu().numpy(), cert_ok.cpu().numpy().astype(bool), cert_status.cpu().numpy(), crl_ok[:n_crls].cpu().numpy().astype(bool),
+                crl_status.cpu().numpy())
