@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from arith_cases import ntt_inputs  # the random input classes, shared with test_arith_cases_cpu.py.  Its `q_minus_1` case is not a
+# large magnitude on the device: k_ntt / k_inv_ntt reduce32 on load, which maps q - 1 to -1 (the edges are test_gpu_arith_edges.py's)
 from gpu_common import host, hp  # noqa: F401
 from oracle import oracle as orc
 
@@ -15,25 +17,6 @@ SETS = {44: (4, 4, 2, 1 << 17), 65: (6, 5, 4, 1 << 19), 87: (8, 7, 2, 1 << 19)}
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
-
-
-def ntt_inputs(rng):
-    cases = {
-        "uniform": rng.integers(0, Q, (37, 256)),
-        "zero": np.zeros((1, 256)),
-        "q_minus_1": np.full((1, 256), Q - 1),
-        "eta": rng.integers(-4, 5, (3, 256)),
-        "gamma1": rng.integers(-(1 << 19) + 1, (1 << 19) + 1, (5, 256)),
-        "gamma1_edges": np.where(rng.integers(0, 2, (2, 256)) == 1, 1 << 19, -(1 << 19) + 1),
-        "t0": rng.integers(-(1 << 12) + 1, (1 << 12) + 1, (2, 256)),
-        "signed_lazy": rng.integers(-9 * Q, 9 * Q, (4, 256)),
-    }
-    c = np.zeros((2, 256), dtype=np.int64)
-    for r in range(2):
-        pos = rng.choice(256, 49, replace=False)
-        c[r, pos] = rng.choice([-1, 1], 49)
-    cases["challenge"] = c
-    return cases
 
 
 def test_ntt_matches_oracle(hp):
