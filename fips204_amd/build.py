@@ -12,7 +12,9 @@ and the issue layers: the certificate-issuing library fips204_amd/x509sign/libml
 writes the request-signing library's descriptors and links the core only, and the request layers: the certification-request library
 fips204_amd/csr/libmldsa_csr.so (include/mldsa_csr.h), which writes the wire-record and the certificate-issuing libraries' descriptors
 and links the core only, and the revocation layers: the revocation-list library fips204_amd/crl/libmldsa_crl.so (include/mldsa_crl.h), which
-writes the wire-record library's descriptors from CRLs, reads the certificate library's rows and links the core only."""
+writes the wire-record library's descriptors from CRLs, reads the certificate library's rows and links the core only, and the path layers: the path-validation library
+fips204_amd/path/libmldsa_path.so (include/mldsa_path.h), which reads the rows of the certificate and the revocation-list library and
+links the core only."""
 import os
 import subprocess
 
@@ -32,9 +34,11 @@ ISSUE_LAYERS = {"x509sign": "libmldsa_x509sign.so"}
 REQUEST_LAYERS = {"csr": "libmldsa_csr.so"}
 # built after REQUEST_LAYERS by the same loop
 REVOCATION_LAYERS = {"crl": "libmldsa_crl.so"}
+# built after REVOCATION_LAYERS by the same loop
+PATH_LAYERS = {"path": "libmldsa_path.so"}
 # PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB, RECSIGN_DIR, RECSIGN_LIB, X509_DIR, X509_LIB, X509SIGN_DIR, X509SIGN_LIB, CSR_DIR, CSR_LIB,
-# CRL_DIR, CRL_LIB
-for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS}.items():
+# CRL_DIR, CRL_LIB, PATH_DIR, PATH_LIB
+for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS}.items():
     globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)
     globals()[f"{_name.upper()}_LIB"] = os.path.join(_HERE, _name, _file)
 
@@ -46,7 +50,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS}.items():
+    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS}.items():
         layer_dir = os.path.join(_HERE, name)
         layer_lib = os.path.join(layer_dir, file)
         if force:

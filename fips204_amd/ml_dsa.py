@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _crl_lib, _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
+from . import _crl_lib, _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _path_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -2183,3 +2183,117 @@ class MlDsaRevocationLists:
             raise RuntimeError("mldsa_crl_table: the lookup table overflowed")
         return (revocation.cpu().numpy(), cert_ok.cpu().numpy().astype(bool), cert_status.cpu().numpy(), crl_ok[:n_crls].cpu().numpy().astype(bool),
                 crl_status.cpu().numpy())
+
+
+# ---- path validation: validity, CA constraints, chain verdicts (include/mldsa_path.h) ---------------------------------------------------
+class MlDsaPathValidator:
+    """The last leg of X.509 path validation on one GPU: libmldsa_path.so (include/mldsa_path.h) behind libmldsa_x509.so, libmldsa_crl.so
+    and libmldsa_rec.so.  blob = uint8 CUDA tensor that holds the certificates and the CRLs (any alignment), certs = uint8 CUDA tensor
+    of mldsa_x509_cert rows (MlDsaCertificates.certs_tensor).  `now` and every time are seconds since 1970-01-01T00:00:00Z.  Name and
+    policy constraints, extended key usage, AKI / SKI, cRLSign, delta and indirect CRLs are not looked at."""
+
+    def __init__(self, device=0, hotpath=None):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _path_lib.load()
+        self.lists = MlDsaRevocationLists(hotpath=self.hp)
+        self.certificates = self.lists.certificates
+        self.records = self.lists.records
+
+    _n = staticmethod(MlDsaRevocationLists._n)
+
+    def parse_device(self, blob, certs, n=None, allow_unknown_critical=False):
+        """mldsa_path_parse, asynchronous on the current stream: policy uint8 [n * 48], to be read as _path_lib.FIELDS_DTYPE."""
+        n = self._n(certs, n, 16, "certs")
+        fields = torch.empty(max(n, 1) * 48, dtype=torch.uint8, device=self.device)
+        _path_lib.check(self.lib.mldsa_path_parse(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), n,
+                                                  _path_lib.ALLOW_UNKNOWN_CRITICAL if allow_unknown_critical else 0, _ptr(fields),
+                                                  _stream(self.device)))
+        return fields[:n * 48]
+
+    def times_device(self, blob, offs):
+        """mldsa_path_times, asynchronous on the current stream: (seconds int64 [n], status uint8 [n]) of the Time TLVs at the blob
+        offsets offs (an int64 CUDA tensor)."""
+        if offs.dtype != torch.int64:
+            raise ValueError("offs: an int64 tensor expected")
+        n = offs.numel()
+        seconds = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        _path_lib.check(self.lib.mldsa_path_times(self.hp._h, _ptr(blob), blob.numel(), _ptr(offs), n, _ptr(seconds), _ptr(status),
+                                                  _stream(self.device)))
+        return seconds[:n], status[:n]
+
+    def crl_times_device(self, blob, crl_fields, crl_status, crl_ok, now, require_next_update=False):
+        """mldsa_path_crl_times, asynchronous on the current stream: (this_s int64 [n], next_s int64 [n], time_status uint8 [n],
+        fresh_ok uint8 [n]).  crl_fields, crl_status: MlDsaRevocationLists.ops_device's; crl_ok: the verdicts on its ops, or None.
+        fresh_ok goes into MlDsaRevocationLists.check_device in the place of crl_ok."""
+        n = self._n(crl_fields, None, 88, "crl_fields")
+        this_s = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        next_s = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        time_status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        fresh_ok = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.device)
+        _path_lib.check(self.lib.mldsa_path_crl_times(self.hp._h, _ptr(blob), blob.numel(), _ptr(crl_fields), _ptr(crl_status),
+                                                      None if crl_ok is None else _ptr(crl_ok), n, int(now),
+                                                      _path_lib.REQUIRE_NEXT_UPDATE if require_next_update else 0, _ptr(this_s), _ptr(next_s),
+                                                      _ptr(time_status), _ptr(fresh_ok), _stream(self.device)))
+        return this_s[:n], next_s[:n], time_status[:n], fresh_ok[:n]
+
+    def chain_device(self, certs, policy, cert_status, cert_ok, revocation, anchor, now, allow_no_crl=False, scratch=None):
+        """mldsa_path_chain, asynchronous on the current stream: results uint8 [n * 8], to be read as _path_lib.RESULT_DTYPE.
+        revocation: MlDsaRevocationLists.check_device's answers, or None; anchor: uint8 [n], nonzero for a trust anchor."""
+        n = self._n(certs, None, 16, "certs")
+        results = torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=self.device)
+        if scratch is None:
+            scratch = torch.empty(max(self.lib.mldsa_path_scratch_bytes(n), 256), dtype=torch.uint8, device=self.device)
+        _path_lib.check(self.lib.mldsa_path_chain(self.hp._h, _ptr(certs), _ptr(policy), _ptr(cert_status), _ptr(cert_ok),
+                                                  None if revocation is None else _ptr(revocation), _ptr(anchor), n, int(now),
+                                                  _path_lib.ALLOW_NO_CRL if allow_no_crl else 0, _ptr(results), _ptr(scratch), scratch.numel(),
+                                                  _stream(self.device)))
+        return results[:n * 8]
+
+    def validate(self, cert_ders, cert_issuers, anchors, now, crl_ders=(), crl_issuers=(), cert_crl=None, pad=0, allow_no_crl=False):
+        """Host lists of DER certificates with their issuers' indices, the indices of the trust anchors, the time, and optionally DER
+        CRLs with the index of the CA certificate that signs each and for every certificate the index of the CRL that covers it (None:
+        none) -> (verdict, where, depth, details).  On one stream: mldsa_x509_ops, mldsa_rec_verify, mldsa_path_parse, and with CRLs
+        mldsa_crl_ops, mldsa_rec_verify, mldsa_crl_table, mldsa_path_crl_times and mldsa_crl_check on fresh_ok, then mldsa_path_chain.
+        Without CRLs revocation is not checked; with them a certificate that no CRL covers is refused (REVOCATION) unless
+        allow_no_crl.  details: the intermediate arrays by name."""
+        n, n_crls = len(cert_ders), len(crl_ders)
+        if len(cert_issuers) != n or (cert_crl is not None and len(cert_crl) != n) or len(crl_issuers) != n_crls:
+            raise ValueError("validate: one issuer per certificate and per CRL, one CRL index (or None) per certificate expected")
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8), {}
+        blob_h, rows = certificates_blob(list(cert_ders) + list(crl_ders), list(cert_issuers) + list(crl_issuers), pad=pad)
+        blob = torch.from_numpy(blob_h.copy()).to(self.device)
+        certs = self.certificates.certs_tensor(rows[:n])
+        anchor_h = np.zeros(n, dtype=np.uint8)
+        anchor_h[list(anchors)] = 1
+        anchor = torch.from_numpy(anchor_h).to(self.device)
+        cert_ok = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        cert_ops, cert_status, cert_fields = self.certificates.ops_device(blob, certs, n)
+        self.records.verify_device(blob, cert_ops, cert_ok, n, MODE_PURE)
+        policy = self.parse_device(blob, certs, n)
+        details = {}
+        revocation = None
+        if n_crls:
+            items = self.lists.items_tensor(_crl_items(rows[n:]))
+            covered = np.array([_crl_lib.NONE if c is None else int(c) for c in (cert_crl or [None] * n)], dtype=np.uint32).view(np.int32)
+            crl_ok = torch.zeros(n_crls, dtype=torch.uint8, device=self.device)
+            max_entries = int(sum(self.lists.lib.mldsa_crl_entries_bound(len(d)) for d in crl_ders))
+            crl_ops, crl_status, crl_fields, entries, totals = self.lists.ops_device(blob, items, cert_fields, n_crls, max_entries)
+            self.records.verify_device(blob, crl_ops, crl_ok, n_crls, MODE_PURE)
+            table, totals = self.lists.table_device(entries, totals)
+            this_s, next_s, time_status, fresh_ok = self.crl_times_device(blob, crl_fields, crl_status, crl_ok, now)
+            revocation = self.lists.check_device(blob, certs, cert_fields, torch.from_numpy(covered.copy()).to(self.device), items, crl_fields,
+                                                 crl_status, fresh_ok, entries, table)
+            details.update(crl_ok=crl_ok, crl_status=crl_status, time_status=time_status, fresh_ok=fresh_ok, this_s=this_s, next_s=next_s,
+                           revocation=revocation)
+        results = self.chain_device(certs, policy, cert_status, cert_ok, revocation, anchor, now, allow_no_crl=allow_no_crl)
+        torch.cuda.synchronize(self.device)
+        if n_crls and int(totals.cpu().numpy().view(_crl_lib.TOTALS_DTYPE)[0]["overflow"]):
+            raise RuntimeError("mldsa_crl_table: the lookup table overflowed")
+        details = {k: v.cpu().numpy() for k, v in details.items()}
+        details.update(cert_ok=cert_ok.cpu().numpy(), cert_status=cert_status.cpu().numpy(),
+                       policy=policy.cpu().numpy().view(_path_lib.FIELDS_DTYPE))
+        res = results.cpu().numpy().view(_path_lib.RESULT_DTYPE)
+        return res["verdict"].copy(), res["where"].copy(), res["depth"].copy(), details
