@@ -14,7 +14,8 @@ fips204_amd/csr/libmldsa_csr.so (include/mldsa_csr.h), which writes the wire-rec
 and links the core only, and the revocation layers: the revocation-list library fips204_amd/crl/libmldsa_crl.so (include/mldsa_crl.h), which
 writes the wire-record library's descriptors from CRLs, reads the certificate library's rows and links the core only, and the path layers: the path-validation library
 fips204_amd/path/libmldsa_path.so (include/mldsa_path.h), which reads the rows of the certificate and the revocation-list library and
-links the core only."""
+links the core only, and the find layers: the path-building library fips204_amd/find/libmldsa_find.so (include/mldsa_find.h), which reads
+the rows of the certificate, the revocation-list and the path-validation library and links the core only."""
 import os
 import subprocess
 
@@ -36,9 +37,11 @@ REQUEST_LAYERS = {"csr": "libmldsa_csr.so"}
 REVOCATION_LAYERS = {"crl": "libmldsa_crl.so"}
 # built after REVOCATION_LAYERS by the same loop
 PATH_LAYERS = {"path": "libmldsa_path.so"}
+# built after PATH_LAYERS by the same loop
+FIND_LAYERS = {"find": "libmldsa_find.so"}
 # PH_DIR, PH_LIB, KEYS_DIR, KEYS_LIB, ... VFY_LIB, RECSIGN_DIR, RECSIGN_LIB, X509_DIR, X509_LIB, X509SIGN_DIR, X509SIGN_LIB, CSR_DIR, CSR_LIB,
-# CRL_DIR, CRL_LIB, PATH_DIR, PATH_LIB
-for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS}.items():
+# CRL_DIR, CRL_LIB, PATH_DIR, PATH_LIB, FIND_DIR, FIND_LIB
+for _name, _file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS, **FIND_LAYERS}.items():
     globals()[f"{_name.upper()}_DIR"] = os.path.join(_HERE, _name)
     globals()[f"{_name.upper()}_LIB"] = os.path.join(_HERE, _name, _file)
 
@@ -50,7 +53,7 @@ def build(force=False, jobs=8):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
     if not os.path.exists(LIB):
         raise RuntimeError(f"build did not produce {LIB}")
-    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS}.items():
+    for name, file in {**LAYERS, **FRONT_LAYERS, **PARSE_LAYERS, **ISSUE_LAYERS, **REQUEST_LAYERS, **REVOCATION_LAYERS, **PATH_LAYERS, **FIND_LAYERS}.items():
         layer_dir = os.path.join(_HERE, name)
         layer_lib = os.path.join(layer_dir, file)
         if force:

@@ -7,11 +7,12 @@ reference's expanded form (src/types.rs:19-41), field by field.  All compute goe
 the C ABI (include/mldsa_hip.h); there is no CPU fallback.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
 
-from . import _crl_lib, _csr_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _path_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
+from . import _crl_lib, _csr_lib, _find_lib, _keycheck_lib, _keys_lib, _lib, _mu_lib, _mus_lib, _path_lib, _ph_lib, _rec_lib, _recsign_lib, _seed_lib, _vfy_lib, _x509_lib, _x509sign_lib
 from .hotpath import HotPath, N, _optr, _ptr, _stream
 
 MODE_PURE, MODE_INTERNAL, MODE_PREHASH = 0, 1, 2
@@ -2199,6 +2200,7 @@ class MlDsaPathValidator:
         self.lists = MlDsaRevocationLists(hotpath=self.hp)
         self.certificates = self.lists.certificates
         self.records = self.lists.records
+        self.builder = None  # an MlDsaPathBuilder, made by the first validate that has to find issuers
 
     _n = staticmethod(MlDsaRevocationLists._n)
 
@@ -2257,8 +2259,17 @@ class MlDsaPathValidator:
         none) -> (verdict, where, depth, details).  On one stream: mldsa_x509_ops, mldsa_rec_verify, mldsa_path_parse, and with CRLs
         mldsa_crl_ops, mldsa_rec_verify, mldsa_crl_table, mldsa_path_crl_times and mldsa_crl_check on fresh_ok, then mldsa_path_chain.
         Without CRLs revocation is not checked; with them a certificate that no CRL covers is refused (REVOCATION) unless
-        allow_no_crl.  details: the intermediate arrays by name."""
+        allow_no_crl.  details: the intermediate arrays by name.
+        cert_issuers None: the issuers are found on the device (MlDsaPathBuilder, include/mldsa_find.h) in front of mldsa_x509_ops;
+        crl_issuers None: the CRLs' issuers too; and where either is None and cert_crl is None, so is the CRL of every certificate.
+        What was found is in details (issuers, candidates, find_status, crl_issuers, cert_crl).  With the arrays given nothing of this
+        runs."""
         n, n_crls = len(cert_ders), len(crl_ders)
+        find_certs, find_crls = cert_issuers is None, crl_issuers is None
+        if find_certs:
+            cert_issuers = [None] * n
+        if find_crls:
+            crl_issuers = [0] * n_crls
         if len(cert_issuers) != n or (cert_crl is not None and len(cert_crl) != n) or len(crl_issuers) != n_crls:
             raise ValueError("validate: one issuer per certificate and per CRL, one CRL index (or None) per certificate expected")
         if n == 0:
@@ -2266,26 +2277,44 @@ class MlDsaPathValidator:
         blob_h, rows = certificates_blob(list(cert_ders) + list(crl_ders), list(cert_issuers) + list(crl_issuers), pad=pad)
         blob = torch.from_numpy(blob_h.copy()).to(self.device)
         certs = self.certificates.certs_tensor(rows[:n])
+        found = None
+        if find_certs or find_crls:
+            if self.builder is None:
+                self.builder = MlDsaPathBuilder(hotpath=self.hp)
+            found = self.builder.build_device(blob, certs)
+            if find_certs:
+                certs = found["certs_out"]
         anchor_h = np.zeros(n, dtype=np.uint8)
         anchor_h[list(anchors)] = 1
         anchor = torch.from_numpy(anchor_h).to(self.device)
         cert_ok = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        cert_ops, cert_status, cert_fields = self.certificates.ops_device(blob, certs, n)
+        if found is None:
+            cert_ops, cert_status, cert_fields = self.certificates.ops_device(blob, certs, n)
+            policy = self.parse_device(blob, certs, n)
+        else:  # both walks were made for the builder, and neither reads an issuer: only the link is left
+            cert_fields, policy = found["fields"], found["policy"]
+            cert_ops = torch.empty(n * 40, dtype=torch.uint8, device=self.device)
+            cert_status = torch.empty(n, dtype=torch.uint8, device=self.device)
+            _x509_lib.check(self.certificates.lib.mldsa_x509_link(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), _ptr(cert_fields), n,
+                                                                  _x509_lib.CHECK_NAMES, _ptr(cert_ops), _ptr(cert_status), _stream(self.device)))
         self.records.verify_device(blob, cert_ops, cert_ok, n, MODE_PURE)
-        policy = self.parse_device(blob, certs, n)
         details = {}
         revocation = None
         if n_crls:
             items = self.lists.items_tensor(_crl_items(rows[n:]))
+            if find_crls:
+                items, found["crl_results"] = self.builder.crl_issuers_device(blob, items, self.builder.crl_parse_device(blob, items), found)
             covered = np.array([_crl_lib.NONE if c is None else int(c) for c in (cert_crl or [None] * n)], dtype=np.uint32).view(np.int32)
+            covered_d = torch.from_numpy(covered.copy()).to(self.device)
+            if found is not None and cert_crl is None:
+                covered_d = found["cert_crl"] = self.builder.cert_crls_device(certs, items, found["scratch"])
             crl_ok = torch.zeros(n_crls, dtype=torch.uint8, device=self.device)
             max_entries = int(sum(self.lists.lib.mldsa_crl_entries_bound(len(d)) for d in crl_ders))
             crl_ops, crl_status, crl_fields, entries, totals = self.lists.ops_device(blob, items, cert_fields, n_crls, max_entries)
             self.records.verify_device(blob, crl_ops, crl_ok, n_crls, MODE_PURE)
             table, totals = self.lists.table_device(entries, totals)
             this_s, next_s, time_status, fresh_ok = self.crl_times_device(blob, crl_fields, crl_status, crl_ok, now)
-            revocation = self.lists.check_device(blob, certs, cert_fields, torch.from_numpy(covered.copy()).to(self.device), items, crl_fields,
-                                                 crl_status, fresh_ok, entries, table)
+            revocation = self.lists.check_device(blob, certs, cert_fields, covered_d, items, crl_fields, crl_status, fresh_ok, entries, table)
             details.update(crl_ok=crl_ok, crl_status=crl_status, time_status=time_status, fresh_ok=fresh_ok, this_s=this_s, next_s=next_s,
                            revocation=revocation)
         results = self.chain_device(certs, policy, cert_status, cert_ok, revocation, anchor, now, allow_no_crl=allow_no_crl)
@@ -2293,7 +2322,149 @@ class MlDsaPathValidator:
         if n_crls and int(totals.cpu().numpy().view(_crl_lib.TOTALS_DTYPE)[0]["overflow"]):
             raise RuntimeError("mldsa_crl_table: the lookup table overflowed")
         details = {k: v.cpu().numpy() for k, v in details.items()}
+        if found is not None:
+            details.update(MlDsaPathBuilder.host_results(found, n, n_crls))
         details.update(cert_ok=cert_ok.cpu().numpy(), cert_status=cert_status.cpu().numpy(),
                        policy=policy.cpu().numpy().view(_path_lib.FIELDS_DTYPE))
         res = results.cpu().numpy().view(_path_lib.RESULT_DTYPE)
         return res["verdict"].copy(), res["where"].copy(), res["depth"].copy(), details
+
+
+class MlDsaPathBuilder:
+    """The front of X.509 path validation on one GPU: libmldsa_find.so (include/mldsa_find.h) finds every certificate's issuer, every
+    CRL's issuer and every certificate's CRL among an unordered bag of certificates, by subject Name, parameter set and key identifier.
+    blob, certs, items: as MlDsaPathValidator's.  seed: 16 bytes that key the table's hash (drawn from the system's generator where
+    None); hash_bits below 64 forces collisions, for tests.  Results never depend on either."""
+
+    def __init__(self, device=0, hotpath=None, seed=None, hash_bits=64):
+        self.hp = hotpath or HotPath(device)
+        self.device = self.hp.device
+        self.lib = _find_lib.load()
+        self.x509, self.crl, self.path = _x509_lib.load(), _crl_lib.load(), _path_lib.load()
+        self.seed = bytes(seed) if seed is not None else os.urandom(16)
+        if len(self.seed) != 16:
+            raise ValueError("seed: 16 bytes expected")
+        self.hash_bits = int(hash_bits)
+
+    _n = staticmethod(MlDsaRevocationLists._n)
+
+    def _rows(self, n, size):
+        return torch.empty(max(n, 1) * size, dtype=torch.uint8, device=self.device)
+
+    def scratch_memory(self, n):
+        return torch.empty(max(self.lib.mldsa_find_scratch_bytes(n), 256), dtype=torch.uint8, device=self.device)
+
+    def parse_device(self, blob, certs):
+        """mldsa_x509_parse and mldsa_path_parse, asynchronous on the current stream: (fields uint8 [n * 56], policy uint8 [n * 48])."""
+        n = self._n(certs, None, 16, "certs")
+        fields, policy = self._rows(n, 56), self._rows(n, 48)
+        _x509_lib.check(self.x509.mldsa_x509_parse(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), n, _ptr(fields), _stream(self.device)))
+        _path_lib.check(self.path.mldsa_path_parse(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), n, 0, _ptr(policy), _stream(self.device)))
+        return fields[:n * 56], policy[:n * 48]
+
+    def crl_parse_device(self, blob, items):
+        """mldsa_crl_parse, asynchronous on the current stream: crl_fields uint8 [n_crls * 88]."""
+        n = self._n(items, None, 16, "items")
+        crl_fields = self._rows(n, 88)
+        _crl_lib.check(self.crl.mldsa_crl_parse(self.hp._h, _ptr(blob), blob.numel(), _ptr(items), n, _ptr(crl_fields), _stream(self.device)))
+        return crl_fields[:n * 88]
+
+    def ids_device(self, blob, certs, policy):
+        """mldsa_find_ids, asynchronous on the current stream: ids uint8 [n * 24], to be read as _find_lib.ID_DTYPE.  policy None: no
+        identifiers are read."""
+        n = self._n(certs, None, 16, "certs")
+        ids = self._rows(n, 24)
+        _find_lib.check(self.lib.mldsa_find_ids(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), None if policy is None else _ptr(policy), n,
+                                                _ptr(ids), _stream(self.device)))
+        return ids[:n * 24]
+
+    def table_device(self, blob, certs, fields, ids, scratch=None):
+        """mldsa_find_table, asynchronous on the current stream: (totals uint8 [16] -- _find_lib.TOTALS_DTYPE --, scratch, which holds the
+        table)."""
+        n = self._n(certs, None, 16, "certs")
+        scratch = self.scratch_memory(n) if scratch is None else scratch
+        totals = self._rows(1, 16)
+        _find_lib.check(self.lib.mldsa_find_table(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), _ptr(fields), _ptr(ids), n, self.seed,
+                                                  self.hash_bits, _ptr(totals), _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return totals, scratch
+
+    def issuers_device(self, blob, certs, fields, ids, totals, scratch, in_place=False):
+        """mldsa_find_issuers, asynchronous on the current stream: (certs_out uint8 [n * 16] -- certs itself with in_place --, results
+        uint8 [n * 12], to be read as _find_lib.RESULT_DTYPE)."""
+        n = self._n(certs, None, 16, "certs")
+        certs_out = certs if in_place else self._rows(n, 16)
+        results = self._rows(n, 12)
+        _find_lib.check(self.lib.mldsa_find_issuers(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), _ptr(fields), _ptr(ids), n, self.seed,
+                                                    self.hash_bits, _ptr(totals), _ptr(scratch), scratch.numel(), _ptr(certs_out), _ptr(results),
+                                                    _stream(self.device)))
+        return certs_out[:n * 16], results[:n * 12]
+
+    def crl_issuers_device(self, blob, items, crl_fields, found):
+        """mldsa_find_crl_issuers, asynchronous on the current stream: (items_out uint8 [n_crls * 16], results uint8 [n_crls * 12]).
+        found: what build_device returned for the certificates."""
+        n_crls = self._n(items, None, 16, "items")
+        n = self._n(found["certs"], None, 16, "certs")
+        items_out, results = self._rows(n_crls, 16), self._rows(n_crls, 12)
+        _find_lib.check(self.lib.mldsa_find_crl_issuers(self.hp._h, _ptr(blob), blob.numel(), _ptr(items), _ptr(crl_fields), n_crls,
+                                                        _ptr(found["certs"]), _ptr(found["fields"]), _ptr(found["ids"]), n, self.seed,
+                                                        self.hash_bits, _ptr(found["totals"]), _ptr(found["scratch"]), found["scratch"].numel(),
+                                                        _ptr(items_out), _ptr(results), _stream(self.device)))
+        return items_out[:n_crls * 16], results[:n_crls * 12]
+
+    def cert_crls_device(self, certs_out, items_out, scratch):
+        """mldsa_find_cert_crls, asynchronous on the current stream: cert_crl int32 [n], -1 (MLDSA_CRL_NONE) where no CRL covers the
+        certificate, as MlDsaRevocationLists.check_device takes it."""
+        n = self._n(certs_out, None, 16, "certs")
+        n_crls = self._n(items_out, None, 16, "items") if items_out is not None else 0
+        cert_crl = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        _find_lib.check(self.lib.mldsa_find_cert_crls(self.hp._h, _ptr(certs_out), n, None if n_crls == 0 else _ptr(items_out), n_crls,
+                                                      _ptr(cert_crl), _ptr(scratch), scratch.numel(), _stream(self.device)))
+        return cert_crl[:n]
+
+    def build_device(self, blob, certs, fields=None, policy=None, use_ids=True):
+        """mldsa_find_build, asynchronous on the current stream, behind parse_device where fields is None: a dict of certs, fields,
+        policy, ids, totals, certs_out, results and scratch.  use_ids False: policy NULL, matching by Name alone."""
+        n = self._n(certs, None, 16, "certs")
+        if fields is None:
+            fields, policy = self.parse_device(blob, certs)
+        ids, totals, certs_out, results, scratch = self._rows(n, 24), self._rows(1, 16), self._rows(n, 16), self._rows(n, 12), self.scratch_memory(n)
+        _find_lib.check(self.lib.mldsa_find_build(self.hp._h, _ptr(blob), blob.numel(), _ptr(certs), _ptr(fields),
+                                                  _ptr(policy) if use_ids and policy is not None else None, n, self.seed, self.hash_bits, _ptr(ids),
+                                                  _ptr(totals), _ptr(certs_out), _ptr(results), _ptr(scratch), scratch.numel(),
+                                                  _stream(self.device)))
+        return dict(certs=certs, fields=fields, policy=policy, ids=ids[:n * 24], totals=totals, certs_out=certs_out[:n * 16],
+                    results=results[:n * 12], scratch=scratch)
+
+    @staticmethod
+    def host_results(found, n, n_crls):
+        """What a build found, as host arrays by name (after a synchronisation)."""
+        res = found["results"].cpu().numpy().view(_find_lib.RESULT_DTYPE)[:n]
+        out = dict(issuers=res["issuer"].copy(), candidates=res["candidates"].copy(), find_status=res["status"].copy(),
+                   ids=found["ids"].cpu().numpy().view(_find_lib.ID_DTYPE)[:n], find_totals=found["totals"].cpu().numpy().view(_find_lib.TOTALS_DTYPE)[0])
+        if "crl_results" in found:
+            crl = found["crl_results"].cpu().numpy().view(_find_lib.RESULT_DTYPE)[:n_crls]
+            out.update(crl_issuers=crl["issuer"].copy(), crl_candidates=crl["candidates"].copy(), crl_find_status=crl["status"].copy())
+        if "cert_crl" in found:
+            out.update(cert_crl=found["cert_crl"].cpu().numpy().view(np.uint32)[:n].copy())
+        return out
+
+    def build(self, cert_ders, crl_ders=(), pad=0, use_ids=True):
+        """Host lists of DER certificates and CRLs in any order -> (issuers uint32 [n], candidates uint32 [n], cert_crl uint32 [n],
+        details): for every certificate the index of its issuer (_find_lib.NO_ISSUER: none found), the number of certificates that
+        matched, and the index of the lowest CRL of its issuer (_find_lib.CRL_NONE: none).  details: find_status, ids, find_totals and,
+        with CRLs, crl_issuers, crl_candidates, crl_find_status."""
+        n, n_crls = len(cert_ders), len(crl_ders)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), {}
+        blob_h, rows = certificates_blob(list(cert_ders) + list(crl_ders), [None] * (n + n_crls), pad=pad)
+        blob = torch.from_numpy(blob_h.copy()).to(self.device)
+        certs = torch.from_numpy(np.ascontiguousarray(rows[:n]).view(np.uint8).reshape(-1).copy()).to(self.device)
+        found = self.build_device(blob, certs, use_ids=use_ids)
+        items_out = None
+        if n_crls:
+            items = torch.from_numpy(_crl_items(rows[n:]).view(np.uint8).reshape(-1).copy()).to(self.device)
+            items_out, found["crl_results"] = self.crl_issuers_device(blob, items, self.crl_parse_device(blob, items), found)
+        found["cert_crl"] = self.cert_crls_device(found["certs_out"], items_out, found["scratch"])
+        torch.cuda.synchronize(self.device)
+        out = self.host_results(found, n, n_crls)
+        return out.pop("issuers"), out.pop("candidates"), out.pop("cert_crl"), out
