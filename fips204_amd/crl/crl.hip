@@ -7,21 +7,21 @@
 //                        the blob; one mldsa_crl_fields row per CRL.
 //   k_crl_place_sums     one CRL per lane: bound_i = revoked_len / 20 of the CRLs whose walk was accepted, summed per workgroup.
 //   k_crl_place_offsets  one wave: the workgroups' sums to exclusive prefixes, in place.
-//   k_crl_place          the same quantity scanned inside the workgroup (wave_inclusive of ../rec/rec_scan.h, the waves' totals through
-//                        LDS): first_i, the SPACE rule, the slots reserved.
+//   k_crl_place          the same quantity scanned inside the workgroup (wave_inclusive of ../rec/rec_wave.h, the waves' totals through
+//                        LDS): first_i, the SPACE rule, the slots reserved.  The first two are the placement scan of ../rec/rec_place.h at
+//                        one quantity; this one keeps its scan written out (rec_place.h says why).
 //   k_crl_entries        one CRL per wave, ENTRY_WAVES per workgroup: a WINDOW of the revoked list in LDS, staged by aligned 16-byte
 //                        loads, one per lane; lane 0 hops from entry header to entry header inside it, the lanes walk one entry each
 //                        and write its row.  The fetch functor reads LDS inside the window and the blob outside it.
 //   k_crl_link           one CRL per wave: the link rule by lane 0, the two Names 64 bytes per step, ops[i], status[i], the totals; the
-//                        slots of a CRL that is refused after all are emptied again.
+//                        slots of a CRL that is refused after all are emptied again.  The comparison and the op's write are those of
+//                        ../x509/x509_dev.h, which k_x509_link shares.
 //   k_crl_insert         one entry slot per lane, grid-stride: the open-addressing table over the entry rows, claimed by atomicCAS.
 //   k_crl_check          one certificate per lane: its serial from its TBS, the probe, one answer byte.
 // What bounds them: latency of the walk's dependent loads in k_crl_parse; in k_crl_entries lane 0's hop, a chain of dependent LDS byte
 // reads per entry, while the list itself is read once through the window; k_crl_insert and k_crl_check are one random 4-byte and one
 // random 32-byte access per probe.  Measured (profiles/crl_bench.jsonl): 4 096 CRLs of 64 entries take mldsa_crl_ops 0.18 ms, 1.4 G
 // entries/s; one CRL of 262 144 entries is one wave's chain and takes 126 ms, about 480 ns per entry.
-// ../rec/rec_scan.h is included for wave_inclusive; its class-scan kernel templates are not instantiated (its one kernel that is no
-// template, k_offsets, is compiled along with the header and never launched).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,7 +30,8 @@
 #include "../../include/mldsa_crl.h"
 #include "../layer/layer_dev.h"
 #include "../layer/layer_host.h"
-#include "../rec/rec_scan.h"
+#include "../rec/rec_place.h"
+#include "../x509/x509_dev.h"
 #include "crl_plan.h"
 
 namespace {
@@ -38,6 +39,9 @@ namespace {
 using namespace mldsa_layer;
 using namespace mldsa_crl;
 using mldsa_rec::wave_inclusive;
+using mldsa_x509::BlobBytes;
+using mldsa_x509::wave_names_differ;
+using mldsa_x509::write_link_op;
 
 static_assert(sizeof(mldsa_crl_item) == 16 && sizeof(mldsa_crl_fields) == 88 && sizeof(mldsa_crl_entry) == 32 && sizeof(mldsa_crl_totals) == 40 &&
                   sizeof(mldsa_rec_op) == 40 && sizeof(mldsa_x509_fields) == 56 && sizeof(mldsa_x509_cert) == 16,
@@ -60,12 +64,6 @@ constexpr int ENTRY_WAVES = 4;    // CRLs per workgroup of k_crl_entries
 constexpr int LINK_WAVES = 4;     // CRLs per workgroup of k_crl_link
 constexpr int TABLE_BLOCK = 256;  // lanes per workgroup of k_crl_insert and k_crl_check
 constexpr uint32_t HEADER_MAX = 6;  // bytes of the longest TLV header read_tlv accepts
-
-// byte pos of the blob, or of a CRL or TBS that begins at `at`; the callers' range checks vouch for the position
-struct BlobBytes {
-    const uint8_t* at;
-    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t pos) const { return at[pos]; }
-};
 
 // byte pos of a CRL of which the part `w` lies in LDS: the window where it holds the position, the blob elsewhere
 struct WindowBytes {
@@ -123,33 +121,16 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_crl_parse(const uint8_t* __restr
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_crl_place_sums(const mldsa_crl_fields* __restrict__ fields, uint32_t n,
                                                                uint64_t* __restrict__ sums) {
-    __shared__ uint64_t part[SCAN_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ uint64_t part[SCAN_WAVES][1];
     const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    uint64_t bound = i < n ? bound_of(fields[i]) : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bound += __shfl_xor((unsigned long long)bound, d, 64);
-    if (lane == 0) part[wave] = bound;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t s = 0;
-#pragma unroll
-        for (int w = 0; w < SCAN_WAVES; ++w) s += part[w];
-        sums[blockIdx.x] = s;
-    }
+    uint64_t bound[1] = {i < n ? bound_of(fields[i]) : 0};
+    mldsa_rec::place_block_sums(bound, part, sums);
 }
 
 // one wave: sums[b] -> the sum over the blocks before b (in place)
 __global__ __launch_bounds__(64) void k_crl_place_offsets(uint64_t* __restrict__ sums, uint32_t n_blocks) {
-    const int lane = threadIdx.x;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n_blocks; base += 64) {
-        const uint32_t b = base + lane;
-        const uint64_t v = b < n_blocks ? sums[b] : 0;
-        const uint64_t inc = wave_inclusive(v, lane);
-        if (b < n_blocks) sums[b] = carry + inc - v;
-        carry += __shfl((unsigned long long)inc, 63, 64);
-    }
+    uint64_t total[1];  // (the sum of all bounds: nobody asks for it)
+    mldsa_rec::place_block_offsets(sums, n_blocks, total);
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_crl_place(mldsa_crl_fields* __restrict__ fields, uint32_t n, const uint64_t* __restrict__ sums,
@@ -181,8 +162,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_crl_place(mldsa_crl_fields* __re
             fields[i].status = ST_SPACE;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) got += __shfl_xor((unsigned long long)got, d, 64);
+    got = wave_sum(got);
     if (lane == 0 && got != 0) atomicAdd((unsigned long long*)&totals->slots, (unsigned long long)got);
 }
 
@@ -320,24 +300,14 @@ __global__ __launch_bounds__(64 * LINK_WAVES) void k_crl_link(const uint8_t* __r
     name_len = (uint32_t)__shfl((int)name_len, 0, 64);
     slot = __shfl((unsigned long long)slot, 0, 64);
     slots = __shfl((unsigned long long)slots, 0, 64);
-    uint32_t diff = 0;
-    for (uint64_t base = 0; base < name_len; base += 64) diff |= name_byte_diff(BlobBytes{blob}, mine, theirs, name_len, base + lane);
-    if (wave_or(diff) != 0) st = ST_NAME;
+    if (wave_names_differ(blob, mine, theirs, name_len, lane)) st = ST_NAME;
     const bool acc = st == ST_OK;
     if (!acc) {  // a refused CRL lists nobody: its slots are emptied again
         uint64_t* rows = reinterpret_cast<uint64_t*>(entries + slot);
         for (uint64_t k = lane; k < 4 * slots; k += 64) rows[k] = 0;
     }
     if (lane == 0) {
-        mldsa_rec_op& op = ops[i];  // every other CRL's op is all zero
-        op.pk_off = acc ? pk_off : 0;
-        op.sig_off = acc ? sig_off : 0;
-        op.msg_off = acc ? tbs_off : 0;
-        op.ctx_off = 0;
-        op.msg_len = acc ? tbs_len : 0;
-        op.ctx_len = 0;
-        op.set = acc ? (uint8_t)set : 0;
-        op.reserved = 0;
+        write_link_op(ops[i], acc, pk_off, sig_off, tbs_off, tbs_len, set);  // every other CRL's op is all zero
         status[i] = (uint8_t)st;
         if (!acc) fields[i].count = 0;
         atomicAdd((unsigned long long*)(acc ? &totals->accepted : &totals->refused), 1ull);

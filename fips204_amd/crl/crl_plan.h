@@ -25,6 +25,7 @@ using mldsa_x509::names_differ;
 using mldsa_x509::OID_LEN;
 using mldsa_x509::oid_set;
 using mldsa_x509::read_tlv;
+using mldsa_x509::same_alg;
 using mldsa_x509::Tlv;
 
 // the status codes, the flag and the caps of include/mldsa_crl.h (crl.hip asserts the equality); 0 ... 6 are include/mldsa_x509.h's
@@ -122,9 +123,9 @@ constexpr uint64_t table_slots(uint64_t max_entries) {
     return t;
 }
 
-constexpr size_t n_blocks(size_t n) { return (n + SCAN_BLOCK - 1) / SCAN_BLOCK; }
+constexpr size_t n_blocks(size_t n) { return mldsa_rec::scan_blocks(n, SCAN_BLOCK); }
 // the working memory of the placement: one 64-bit sum per workgroup of the scan, rounded up to 256 bytes; 0 past MAX_CRLS
-constexpr size_t scratch_bytes(size_t n_crls) { return n_crls > MAX_CRLS ? 0 : mldsa_rec::up256(8 * n_blocks(n_crls)); }
+constexpr size_t scratch_bytes(size_t n_crls) { return n_crls > MAX_CRLS ? 0 : mldsa_rec::place_sums_bytes(n_crls, SCAN_BLOCK, 1); }
 
 // CRL i, whose header walk was accepted, has its slots at [first, first + bound) where they lie inside the table; else ST_SPACE
 constexpr int place_status(uint64_t first, uint64_t bound, uint64_t max_entries) { return first + bound > max_entries ? ST_SPACE : ST_OK; }
@@ -214,9 +215,7 @@ constexpr CrlWalk walk_crl(const Fetch& f, uint32_t len) {
     w.issuer_len = issuer.at + issuer.len - w.issuer_off;
     // ALG: the outer algorithm, and the inner one byte for byte the same TLV (the outer one is 30 0B and OID_LEN bytes by now)
     const uint32_t sset = alg.len == OID_LEN ? oid_set(f, alg.at) : 0;
-    bool same = sset != 0 && inner.len == OID_LEN;
-    for (uint32_t j = 0; j < OID_LEN; ++j)
-        if (same && f(inner.at + j) != f(alg.at + j)) same = false;
+    const bool same = sset != 0 && inner.len == OID_LEN && same_alg(f, inner.at, alg.at);
     w.status = ST_ALG;
     if (!same) return w;
     w.status = ST_SIG;
@@ -315,14 +314,11 @@ constexpr Serial cert_serial(const Fetch& f, uint32_t tbs_len) {
 }
 
 // ---- the link rule ----------------------------------------------------------------------------------------------------------------------
-// The status of CRL i after walk, placement and entries (own_status, own_sig_set) and before the Names are compared.  `issuer` is a
-// row of the certificates' fields; issuer_status and issuer_key_set are read from it only where issuer < n_certs (pass 0 otherwise).
+// The status of CRL i after walk, placement and entries (own_status, own_sig_set) and before the Names are compared: the certificate's
+// rule without its "no issuer" case.  A CRL always names an issuer: 0xFFFFFFFF is an index like any other and, with n_certs at most
+// 2^30, out of range.
 constexpr int link_status(int own_status, uint32_t own_sig_set, uint32_t issuer, uint64_t n_certs, int issuer_status, uint32_t issuer_key_set) {
-    if (own_status != ST_OK) return own_status;
-    if (issuer >= n_certs) return ST_ISSUER;
-    if (issuer_status == ST_RANGE || issuer_status == ST_DER) return ST_ISSUER;
-    if (issuer_key_set == 0 || issuer_key_set != own_sig_set) return ST_ISSUER;
-    return ST_OK;
+    return mldsa_x509::signer_status(own_status, own_sig_set, issuer, n_certs, issuer_status, issuer_key_set);
 }
 
 // ---- the lookup's answer ----------------------------------------------------------------------------------------------------------------

@@ -9,18 +9,17 @@
 //                    TLV headers; status[i], tbs_len (0 when refused) and, per workgroup, the sum of the lengths and the count of
 //                    accepted requests.
 //   k_csr_offsets    one wave: the workgroups' two sums to exclusive prefixes (in place), and the totals.
-//   k_csr_apply      the same two quantities scanned inside the workgroup (wave_inclusive of ../rec/rec_scan.h, the waves' totals
-//                    through LDS): every TBSCertificate's offset in `out`, the SPACE rule, reqs_out[i], status[i].  The one request
-//                    whose range straddles out_len -- the first that does not fit -- corrects the totals' counts.
+//   k_csr_apply      the same two quantities scanned inside the workgroup (the wave scans, the waves' totals through LDS): every
+//                    TBSCertificate's offset in `out`, the SPACE rule, reqs_out[i], status[i].  The one request whose range straddles
+//                    out_len -- the first that does not fit -- corrects the totals' counts.
 //   k_csr_tbs_write  one request per wave, WRITE_WAVES per workgroup: 24 fixed bytes by single lanes, the six pieces by copy_field of
-//                    ../rec/rec_scan.h (aligned 16-byte loads, funnel-shifted, aligned 16-byte stores, single bytes at the ends).
+//                    ../rec/rec_wave.h (aligned 16-byte loads, funnel-shifted, aligned 16-byte stores, single bytes at the ends).
+// The scan of the three middle kernels is the placement scan of ../rec/rec_place.h, which libmldsa_x509sign.so shares.
 // What bounds them: latency of the walk's dependent loads in k_csr_parse and of the template headers' in k_csr_check; k_csr_tbs_write
 // reads and writes tbs_len bytes per request, 1.4 ... 2.7 KB in six pieces of which four are under 64 bytes, so a wave's life is its
 // prologue and six dependent load-store steps: measured 1.5 / 2.0 / 2.4 TB/s for ML-DSA-44 / 65 / 87 where a plain copy reaches 4.4 ... 5.1
 // (profiles/csr_bench.jsonl).  What helps is waves in flight: the wave's three rows are read through scalar loads, which keeps the
 // kernel at 58 VGPRs and eight waves per SIMD.
-// ../rec/rec_scan.h is included for wave_inclusive and copy_field; its class-scan kernel templates are not instantiated (its one kernel
-// that is no template, k_offsets, is compiled along with the header and never launched).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,7 +27,8 @@
 
 #include "../../include/mldsa_csr.h"
 #include "../layer/layer_host.h"
-#include "../rec/rec_scan.h"
+#include "../rec/rec_place.h"
+#include "../x509/x509_dev.h"
 #include "csr_plan.h"
 
 namespace {
@@ -36,7 +36,8 @@ namespace {
 using namespace mldsa_layer;
 using namespace mldsa_csr;
 using mldsa_rec::copy_field;
-using mldsa_rec::wave_inclusive;
+using mldsa_rec::PLACE_SUMS;
+using mldsa_x509::BlobBytes;
 
 static_assert(sizeof(mldsa_csr_item) == 16 && sizeof(mldsa_csr_fields) == 56 && sizeof(mldsa_csr_issue) == 64 &&
                   sizeof(mldsa_csr_totals) == 24 && sizeof(mldsa_rec_op) == 40 && sizeof(mldsa_x509sign_req) == 32,
@@ -51,12 +52,6 @@ static_assert(FLAG_RND == MLDSA_CSR_RND && FLAG_RND == MLDSA_X509SIGN_RND && SER
 
 constexpr int SCAN_WAVES = SCAN_BLOCK / 64;
 constexpr int WRITE_WAVES = 4;  // requests per workgroup of k_csr_tbs_write
-
-// byte pos of the blob, or of a request that begins at `at`; the callers' range checks vouch for the position
-struct BlobBytes {
-    const uint8_t* at;
-    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t pos) const { return at[pos]; }
-};
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_csr_parse(const uint8_t* __restrict__ blob, uint64_t blob_len,
                                                           const mldsa_csr_item* __restrict__ items, uint32_t n,
@@ -100,8 +95,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_csr_check(const uint8_t* __restr
                                                           const mldsa_csr_issue* __restrict__ entries, const uint8_t* __restrict__ ok,
                                                           uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ lens,
                                                           uint64_t* __restrict__ sums) {
-    __shared__ uint64_t part[SCAN_WAVES][SUMS_PER_BLOCK];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ uint64_t part[SCAN_WAVES][PLACE_SUMS];
     const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
     uint64_t bytes = 0, count = 0;  // no request: counted nowhere
     if (i < n) {
@@ -115,52 +109,23 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_csr_check(const uint8_t* __restr
         status[i] = (uint8_t)st;
         lens[i] = (uint32_t)bytes;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        bytes += __shfl_xor((unsigned long long)bytes, d, 64);
-        count += __shfl_xor((unsigned long long)count, d, 64);
-    }
-    if (lane == 0) {
-        part[wave][0] = bytes;
-        part[wave][1] = count;
-    }
-    __syncthreads();
-    if (threadIdx.x < SUMS_PER_BLOCK) {
-        uint64_t s = 0;
-#pragma unroll
-        for (int w = 0; w < SCAN_WAVES; ++w) s += part[w][threadIdx.x];
-        sums[(size_t)blockIdx.x * SUMS_PER_BLOCK + threadIdx.x] = s;
-    }
+    uint64_t v[PLACE_SUMS] = {bytes, count};
+    mldsa_rec::place_block_sums(v, part, sums);
 }
 
 // one wave: sums[b][q] -> the sum over the blocks before b (in place); the totals as they stand when every TBSCertificate fits
 __global__ __launch_bounds__(64) void k_csr_offsets(uint64_t* __restrict__ sums, uint32_t n_blocks, uint32_t n,
                                                     mldsa_csr_totals* __restrict__ totals) {
-    const int lane = threadIdx.x;
-    uint64_t carry[SUMS_PER_BLOCK] = {0, 0};
-    for (uint32_t base = 0; base < n_blocks; base += 64) {
-        const uint32_t b = base + lane;
-#pragma unroll
-        for (int q = 0; q < (int)SUMS_PER_BLOCK; ++q) {
-            const uint64_t v = b < n_blocks ? sums[(size_t)b * SUMS_PER_BLOCK + q] : 0;
-            const uint64_t inc = wave_inclusive(v, lane);
-            if (b < n_blocks) sums[(size_t)b * SUMS_PER_BLOCK + q] = carry[q] + inc - v;
-            carry[q] += __shfl((unsigned long long)inc, 63, 64);
-        }
-    }
-    if (lane == 0) {
-        totals->accepted = carry[1];
-        totals->refused = n - carry[1];
-        totals->out_bytes = carry[0];
-    }
+    uint64_t total[PLACE_SUMS];
+    mldsa_rec::place_block_offsets(sums, n_blocks, total);
+    if (threadIdx.x == 0) mldsa_rec::place_totals(totals, n, total);
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_csr_apply(const mldsa_csr_issue* __restrict__ entries, uint32_t n, uint64_t out_len,
                                                           const uint32_t* __restrict__ lens, const uint64_t* __restrict__ sums,
                                                           mldsa_x509sign_req* __restrict__ reqs_out, uint8_t* __restrict__ status,
                                                           mldsa_csr_totals* __restrict__ totals) {
-    __shared__ uint64_t part[SCAN_WAVES][SUMS_PER_BLOCK];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ uint64_t part[SCAN_WAVES][PLACE_SUMS];
     const uint32_t i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
     int st = ST_OK;
     uint64_t bytes = 0, count = 0;
@@ -171,29 +136,13 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_csr_apply(const mldsa_csr_issue*
             count = 1;
         }
     }
-    const uint64_t bytes_inc = wave_inclusive(bytes, lane), count_inc = wave_inclusive(count, lane);
-    if (lane == 63) {
-        part[wave][0] = bytes_inc;
-        part[wave][1] = count_inc;
-    }
-    __syncthreads();
+    const uint64_t v[PLACE_SUMS] = {bytes, count};
+    uint64_t inc[PLACE_SUMS], before[PLACE_SUMS];
+    mldsa_rec::place_wave_scan(v, part, inc);
     if (i >= n) return;
-    // what the blocks before, the waves before and the lanes before add up to
-    uint64_t at = sums[(size_t)blockIdx.x * SUMS_PER_BLOCK] + bytes_inc - bytes;
-    uint64_t before = sums[(size_t)blockIdx.x * SUMS_PER_BLOCK + 1] + count_inc - count;
-    for (int w = 0; w < SCAN_WAVES; ++w) {
-        if (w >= wave) break;
-        at += part[w][0];
-        before += part[w][1];
-    }
-    if (st == ST_OK && !in_range(at, bytes, out_len)) {
-        st = ST_SPACE;
-        // Offsets only grow: the requests in front of the one that straddles out_len fit, it and all behind it do not.
-        if (at <= out_len) {
-            totals->accepted = before;
-            totals->refused = n - before;
-        }
-    }
+    mldsa_rec::place_before(v, inc, part, sums, before);
+    const uint64_t at = before[0];
+    if (st == ST_OK && !mldsa_rec::place_fits(at, bytes, out_len, before[1], n, totals)) st = ST_SPACE;
     const bool acc = st == ST_OK;  // every other request's row is all zero
     const mldsa_csr_issue& e = entries[i];
     mldsa_x509sign_req q = {};
@@ -262,10 +211,7 @@ int check_plan(const char* fn, const uint8_t* ok, size_t n, const mldsa_csr_tota
 
 int check_write(const char* fn, const uint8_t* blob, uint64_t blob_len, const uint8_t* out, uint64_t out_len) {
     if (!out && out_len != 0) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": NULL pointer");
-    // the two pointer ranges (as integers: nothing is added to a pointer that might not hold it)
-    const uintptr_t b = (uintptr_t)blob, o = (uintptr_t)out;
-    const bool apart = blob_len == 0 || out_len == 0 || (b >= o && b - o >= out_len) || (o >= b && o - b >= blob_len);
-    if (!apart) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": out overlaps the blob");
+    if (!ranges_apart(blob, blob_len, out, out_len)) return fail(MLDSA_ERR_PARAM, std::string(fn) + ": out overlaps the blob");
     return MLDSA_OK;
 }
 

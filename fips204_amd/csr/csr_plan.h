@@ -30,10 +30,10 @@ using mldsa_rec::CLASS_REFUSED;
 using mldsa_rec::in_range;
 using mldsa_rec::pk_len;
 using mldsa_rec::sig_len;
-using mldsa_rec::up256;
 using mldsa_x509::oid_set;
 using mldsa_x509::OID_LEN;
 using mldsa_x509::read_tlv;
+using mldsa_x509::same_alg;
 using mldsa_x509::Tlv;
 using mldsa_x509sign::max_tbs_len;
 
@@ -99,9 +99,7 @@ constexpr Walk walk(const Fetch& f, uint32_t len) {
     if (set == 0) return w;
     // the SPKI's algorithm byte for byte the outer one (both contents are OID_LEN bytes by now), the key of that set's length
     w.status = ST_KEY;
-    bool same = kalg.len == OID_LEN;
-    for (uint32_t j = 0; j < OID_LEN; ++j)
-        if (same && f(kalg.at + j) != f(alg.at + j)) same = false;
+    const bool same = kalg.len == OID_LEN && same_alg(f, kalg.at, alg.at);
     if (!same || key.len != 1 + pk_len(class_of_set(set)) || f(key.at) != 0) return w;
     w.status = ST_SIG;
     if (sig.len != 1 + sig_len(class_of_set(set)) || f(sig.at) != 0) return w;
@@ -219,10 +217,10 @@ constexpr uint64_t piece_off(const mldsa_csr_issue& e, const mldsa_csr_fields& r
 }
 
 // ---- the working memory (include/mldsa_csr.h spells the formula out) --------------------------------------------------------------------------
+// the placement scan's of ../rec/rec_plan.h under this library's block and cap: the sums of TBS lengths and accepted requests, the lengths
 constexpr size_t MAX_REQUESTS = (size_t)1 << 30;
-constexpr size_t SUMS_PER_BLOCK = 2;  // the workgroup's sum of TBS lengths and its count of accepted requests
-constexpr size_t n_blocks(size_t n) { return (n + SCAN_BLOCK - 1) / SCAN_BLOCK; }
-constexpr size_t plan_sums_bytes(size_t n) { return up256(8 * SUMS_PER_BLOCK * n_blocks(n)); }
-constexpr size_t plan_bytes(size_t n) { return n > MAX_REQUESTS ? 0 : plan_sums_bytes(n) + up256(4 * n); }
+constexpr size_t n_blocks(size_t n) { return mldsa_rec::scan_blocks(n, SCAN_BLOCK); }
+constexpr size_t plan_sums_bytes(size_t n) { return mldsa_rec::place_sums_bytes(n, SCAN_BLOCK, mldsa_rec::PLACE_SUMS); }
+constexpr size_t plan_bytes(size_t n) { return mldsa_rec::place_plan_bytes(n, SCAN_BLOCK, MAX_REQUESTS); }
 
 }  // namespace mldsa_csr

@@ -22,12 +22,14 @@
 #include "../../include/mldsa_find.h"
 #include "../layer/layer_dev.h"
 #include "../layer/layer_host.h"
+#include "../x509/x509_dev.h"
 #include "find_plan.h"
 
 namespace {
 
 using namespace mldsa_layer;
 using namespace mldsa_find;
+using mldsa_x509::BlobBytes;
 
 static_assert(sizeof(mldsa_find_id) == ID_BYTES && offsetof(mldsa_find_id, aki_off) == ID_AKI_OFF && offsetof(mldsa_find_id, ski_len) == ID_SKI_LEN &&
                   offsetof(mldsa_find_id, aki_len) == ID_AKI_LEN && offsetof(mldsa_find_id, status) == ID_STATUS &&
@@ -48,12 +50,6 @@ static_assert(MAX_EXTS == MLDSA_PATH_MAX_EXTS && MAX_KEYID == MLDSA_FIND_MAX_KEY
 
 constexpr int IDS_BLOCK = 256;  // items per workgroup of the lane-per-item kernels
 constexpr int WAVES = 4;        // items per workgroup of the wave-per-item kernels
-
-// byte pos of the blob, or of a certificate that begins at `at`; the callers' range checks vouch for the position
-struct BlobBytes {
-    const uint8_t* at;
-    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t pos) const { return at[pos]; }
-};
 
 // the rows of the certificates, as every kernel behind k_find_ids takes them
 struct Certs {
@@ -95,12 +91,6 @@ __device__ __forceinline__ bool candidate_key(const Certs& C, uint32_t j, uint32
     out->id_off = has_ski ? d.ski_off : 0;
     out->id_len = has_ski ? d.ski_len : 0u;
     return true;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m, 64);
-    return v;
 }
 
 // key_hash of find_plan.h, the same value in every lane: lane l adds the bytes l, l + 64, ...

@@ -1,5 +1,5 @@
-// The device helpers the layered libraries' kernels share (mu/, seed/, keycheck/; ph/stream.hip and mus/ take wave_max): the wave-wide OR
-// and maximum, the canonical representative, and the shapes two or more of them agree on -- the LDS tile of the lane-per-state SHAKE256
+// The device helpers the layered libraries' kernels share (mu/, seed/, keycheck/; ph/stream.hip and mus/ take wave_max; crl/ and find/
+// take wave_sum): the wave-wide OR, sum and maximum, the canonical representative, and the shapes two or more of them agree on -- the LDS tile of the lane-per-state SHAKE256
 // and the packed t1 row.  Helpers only: every
 // kernel (__global__) stays in its library's .hip file.  The core's device headers are included read-only.
 //
@@ -35,6 +35,13 @@ constexpr int T1_ROW_DW = 80;  // a row of t1 in a wire public key: 256 coeffici
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+
+// sum over the wave, the same value in every lane
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m, 64);
     return v;
 }
 

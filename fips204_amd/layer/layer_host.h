@@ -71,6 +71,13 @@ struct DeviceScope {
 // --------------------------------------------------------------------------------------------------------------- scratch
 bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+// An output buffer does not overlap the blob it is filled from: decided from the two pointer ranges as integers (nothing is added to a
+// pointer that might not hold it).  An empty range overlaps nothing.
+bool ranges_apart(const void* blob, uint64_t blob_len, const void* out, uint64_t out_len) {
+    const uintptr_t b = (uintptr_t)blob, o = (uintptr_t)out;
+    return blob_len == 0 || out_len == 0 || (b >= o && b - o >= out_len) || (o >= b && o - b >= blob_len);
+}
+
 // Bump allocator of a scratch layout: take() returns the part's offset; every part is rounded up to `round` bytes.
 struct Taker {
     size_t at = 0, round = 1;

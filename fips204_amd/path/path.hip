@@ -19,12 +19,14 @@
 #include "../../include/mldsa_path.h"
 #include "../layer/layer_dev.h"
 #include "../layer/layer_host.h"
+#include "../x509/x509_dev.h"
 #include "path_plan.h"
 
 namespace {
 
 using namespace mldsa_layer;
 using namespace mldsa_path;
+using mldsa_x509::BlobBytes;
 
 static_assert(sizeof(mldsa_path_fields) == FIELDS_BYTES && offsetof(mldsa_path_fields, not_after) == FIELDS_NOT_AFTER &&
                   offsetof(mldsa_path_fields, ext_off) == FIELDS_EXT_OFF && offsetof(mldsa_path_fields, crit_off) == FIELDS_CRIT_OFF &&
@@ -54,12 +56,6 @@ static_assert(FLAG_ALLOW_UNKNOWN_CRITICAL == MLDSA_PATH_ALLOW_UNKNOWN_CRITICAL &
               "the flags and the caps of include/mldsa_path.h; n_ext and depth are one byte each");
 
 constexpr int PATH_BLOCK = 256;  // items per workgroup of every kernel here
-
-// byte pos of a certificate or of a Time's surroundings that begin at `at`; the callers' range checks vouch for the position
-struct BlobBytes {
-    const uint8_t* at;
-    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t pos) const { return at[pos]; }
-};
 
 // packed node a of the scratch array; climb vouches for a < n
 struct Nodes {

@@ -98,4 +98,13 @@ constexpr size_t SCAN_BLOCK = 256;   // MLDSA_REC_SCAN_BLOCK
 constexpr size_t SCAN_VALUES = 10;   // per block: the four class counts, message bytes and context bytes of the three accepted classes
 constexpr size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
+// The working memory of the placement scan (rec_place.h) over n items in workgroups of `block`: `q` 64-bit sums per workgroup, and for
+// the two libraries that lay out an output buffer (q = PLACE_SUMS) one 32-bit length per item behind them; 0 past the library's cap.
+constexpr size_t PLACE_SUMS = 2;  // the workgroup's sum of output lengths and its count of accepted items
+constexpr size_t scan_blocks(size_t n, size_t block) { return (n + block - 1) / block; }
+constexpr size_t place_sums_bytes(size_t n, size_t block, size_t q) { return up256(8 * q * scan_blocks(n, block)); }
+constexpr size_t place_plan_bytes(size_t n, size_t block, size_t cap) {
+    return n > cap ? 0 : place_sums_bytes(n, block, PLACE_SUMS) + up256(4 * n);
+}
+
 }  // namespace mldsa_rec

@@ -1,5 +1,6 @@
 // The device code the record libraries share (libmldsa_rec.so, libmldsa_recsign.so): the three kernels of the plan -- classify, offsets,
-// apply: a stable exclusive scan of ten quantities per op -- and the wave's copy of an unaligned field by the copy plan of rec_plan.h.
+// apply: a stable exclusive scan of ten quantities per op.  The wave's scan and the wave's copy of an unaligned field, which the
+// certificate layers take as well, are in rec_wave.h.
 // Each library instantiates the kernels on its descriptor type `Op` (which has msg_len and ctx_len) and, for k_classify, on its `Check`:
 // a small struct passed by value that holds what a descriptor is checked against and whose __device__ call operator returns the
 // descriptor's class.  k_pack and k_scatter are each library's own and stay in its .hip file (../layer/layer_dev.h).
@@ -16,6 +17,7 @@
 #include <stdint.h>
 
 #include "rec_plan.h"
+#include "rec_wave.h"
 
 namespace mldsa_rec {
 namespace {
@@ -32,15 +34,6 @@ __device__ __forceinline__ void op_values(int cls, uint32_t msg_len, uint32_t ct
         v[4 + c] = cls == c ? msg_len : 0;
         v[7 + c] = cls == c ? ctx_len : 0;
     }
-}
-
-__device__ __forceinline__ uint64_t wave_inclusive(uint64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t u = __shfl_up((unsigned long long)v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
 }
 
 // one op per thread, SCAN_BLOCK per workgroup: check(descriptor) gives the op's class; the workgroup's ten sums go to sums[block]
@@ -143,32 +136,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_apply(const Op* __restrict__ ops
     class_slot[i] = ((uint32_t)cls << 30) | ((uint32_t)slot & SLOT_MASK);
     msg_pos[i] = mp;
     ctx_pos[i] = cp;
-}
-
-// ---- the copy ---------------------------------------------------------------------------------------------------------------------------
-// `len` bytes from offset `off` of a window of `window_len` bytes (the range lies inside it: the range check passed) to dst, by the
-// whole wave.  The window is the blob for a field of a record, a class's sigs array for libmldsa_recsign.so's scatter.  `base` is the
-// window's address rounded down to 16 and mis = window - base: the frame of rec_plan.h.  Every wide load lies inside the window, every
-// wide store inside [dst, dst + len).
-__device__ __forceinline__ void copy_field(const uint8_t* __restrict__ base, uint32_t mis, uint64_t window_len, uint64_t off, uint32_t len,
-                                           uint8_t* __restrict__ dst, int lane) {
-    const uint64_t src = mis + off;
-    const CopyPlan p = copy_plan(src, len, (uint64_t)(uintptr_t)dst, mis, mis + window_len);
-    for (uint32_t b = lane; b < p.head; b += 64) dst[b] = base[src + b];
-    uint8_t* body = dst + p.head;
-#pragma unroll 2
-    for (uint64_t c = lane; c < p.body; c += 64) {
-        const uint64_t at = chunk_src(p, src, c);
-        const uint4 lo = *reinterpret_cast<const uint4*>(base + at);
-        uint4 hi = make_uint4(0, 0, 0, 0);
-        if (p.shift != 0) hi = *reinterpret_cast<const uint4*>(base + at + 16);
-        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        uint32_t o[4];
-        funnel16(w, p.shift, o);
-        *reinterpret_cast<uint4*>(body + 16 * c) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    const uint64_t done = p.head + 16 * p.body;
-    for (uint32_t b = lane; b < p.tail; b += 64) dst[done + b] = base[src + done + b];
 }
 
 }  // namespace

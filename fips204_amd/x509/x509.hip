@@ -7,7 +7,8 @@
 //                 has one such chain, so the launch keeps as many in flight as there are lanes.
 //   k_x509_link   one certificate per wave, LINK_WAVES per workgroup: lane 0 reads the certificate's row and its issuer's row and
 //                 decides by the link rule of x509_plan.h, the decision is broadcast, and with CHECK_NAMES the wave compares the two
-//                 Name TLVs 64 bytes per step (one byte of each per lane, OR-reduced).  Lane 0 writes ops[i] and status[i].
+//                 Name TLVs 64 bytes per step (one byte of each per lane, OR-reduced).  Lane 0 writes ops[i] and status[i].  The
+//                 comparison and the op's write are those of x509_dev.h, which k_crl_link shares.
 // What bounds them: latency of the dependent loads in k_x509_parse; k_x509_link reads two 56-byte rows and two Names and writes 41 bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +18,7 @@
 #include "../../include/mldsa_x509.h"
 #include "../layer/layer_dev.h"
 #include "../layer/layer_host.h"
+#include "x509_dev.h"
 #include "x509_plan.h"
 
 namespace {
@@ -33,12 +35,6 @@ static_assert(FLAG_CHECK_NAMES == MLDSA_X509_CHECK_NAMES && NO_ISSUER == MLDSA_X
 
 constexpr int PARSE_BLOCK = 256;  // certificates per workgroup of k_x509_parse
 constexpr int LINK_WAVES = 4;     // certificates per workgroup of k_x509_link
-
-// byte pos of the blob, or of a certificate that begins at `at`; the callers' range checks vouch for the position
-struct BlobBytes {
-    const uint8_t* at;
-    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t pos) const { return at[pos]; }
-};
 
 __global__ __launch_bounds__(PARSE_BLOCK) void k_x509_parse(const uint8_t* __restrict__ blob, uint64_t blob_len,
                                                             const mldsa_x509_cert* __restrict__ certs, uint32_t n,
@@ -108,20 +104,9 @@ __global__ __launch_bounds__(64 * LINK_WAVES) void k_x509_link(const uint8_t* __
     mine = __shfl((unsigned long long)mine, 0, 64);
     theirs = __shfl((unsigned long long)theirs, 0, 64);
     name_len = (uint32_t)__shfl((int)name_len, 0, 64);
-    uint32_t diff = 0;
-    for (uint64_t base = 0; base < name_len; base += 64) diff |= name_byte_diff(BlobBytes{blob}, mine, theirs, name_len, base + lane);
-    if (wave_or(diff) != 0) st = ST_NAME;
+    if (wave_names_differ(blob, mine, theirs, name_len, lane)) st = ST_NAME;
     if (lane == 0) {
-        const bool acc = st == ST_OK;  // every other certificate's op is all zero
-        mldsa_rec_op& op = ops[i];
-        op.pk_off = acc ? pk_off : 0;
-        op.sig_off = acc ? sig_off : 0;
-        op.msg_off = acc ? tbs_off : 0;
-        op.ctx_off = 0;
-        op.msg_len = acc ? tbs_len : 0;
-        op.ctx_len = 0;
-        op.set = acc ? (uint8_t)set : 0;
-        op.reserved = 0;
+        write_link_op(ops[i], st == ST_OK, pk_off, sig_off, tbs_off, tbs_len, set);  // every other certificate's op is all zero
         status[i] = (uint8_t)st;
     }
 }

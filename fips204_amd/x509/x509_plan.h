@@ -74,6 +74,18 @@ constexpr uint32_t oid_set(const Fetch& f, uint32_t pos) {
     return b == 0x11 ? 44 : b == 0x12 ? 65 : b == 0x13 ? 87 : 0;
 }
 
+// the OID_LEN bytes at a_at and at b_at are the same, byte for byte.  The caller vouches for both ranges: the contents of two
+// AlgorithmIdentifiers of OID_LEN bytes each.  The walks of a certificate, a CRL and a certification request call this; their signed
+// envelope and ALG / SIG rule stay written out in each, because as functions they change the registers of the kernels that inline them
+// (the rule of ../layer/layer_dev.h; DESIGN.md has the numbers).
+template <class Fetch>
+constexpr bool same_alg(const Fetch& f, uint32_t a_at, uint32_t b_at) {
+    bool same = true;
+    for (uint32_t j = 0; j < OID_LEN; ++j)
+        if (same && f(a_at + j) != f(b_at + j)) same = false;
+    return same;
+}
+
 // ---- the walk ---------------------------------------------------------------------------------------------------------------------------
 // What the walk finds, relative to the certificate.  A status of ST_DER leaves everything else 0.  sig_off and sig_set are nonzero only
 // where the status is ST_OK; key_off and key_set only where the subject key is an ML-DSA key of the right length.
@@ -134,9 +146,7 @@ constexpr Walk walk(const Fetch& f, uint32_t len) {
     }
     // the outer algorithm, and the inner one byte for byte the same TLV (the outer one is 30 0B and OID_LEN bytes by now)
     const uint32_t sset = alg.len == OID_LEN ? oid_set(f, alg.at) : 0;
-    bool same = sset != 0 && inner.len == OID_LEN;  // (a minimal length: both headers are 30 0B)
-    for (uint32_t j = 0; j < OID_LEN; ++j)
-        if (same && f(inner.at + j) != f(alg.at + j)) same = false;
+    const bool same = sset != 0 && inner.len == OID_LEN && same_alg(f, inner.at, alg.at);  // (a minimal length: both headers are 30 0B)
     w.status = ST_ALG;
     if (!same) return w;
     w.status = ST_SIG;
@@ -148,16 +158,23 @@ constexpr Walk walk(const Fetch& f, uint32_t len) {
 }
 
 // ---- the link rule ----------------------------------------------------------------------------------------------------------------------
-// The status of certificate i after its own walk (own_status, own_sig_set) and before the names are compared.  `issuer` is its issuer's
-// index; issuer_status and issuer_key_set are read from the issuer's fields row only where issuer < n (pass 0 otherwise).  An issuer
-// whose own status is ST_ALG or ST_SIG (or anything the link gave it) still lends its key.
-constexpr int link_status(int own_status, uint32_t own_sig_set, uint32_t issuer, uint64_t n, int issuer_status, uint32_t issuer_key_set) {
+// The status of a signed item (a certificate, a CRL) after its own walk (own_status, own_sig_set) and before the names are compared.
+// `issuer` is its issuer's index among n certificates; issuer_status and issuer_key_set are read from the issuer's fields row only
+// where issuer < n (pass 0 otherwise).  An issuer whose own status is ST_ALG or ST_SIG (or anything the link gave it) still lends its
+// key.
+constexpr int signer_status(int own_status, uint32_t own_sig_set, uint32_t issuer, uint64_t n, int issuer_status, uint32_t issuer_key_set) {
     if (own_status != ST_OK) return own_status;
-    if (issuer == NO_ISSUER) return ST_PARSE_ONLY;
     if (issuer >= n) return ST_ISSUER;
     if (issuer_status == ST_RANGE || issuer_status == ST_DER) return ST_ISSUER;
     if (issuer_key_set == 0 || issuer_key_set != own_sig_set) return ST_ISSUER;
     return ST_OK;
+}
+
+// the certificate's: a certificate may name no issuer at all and is then parsed only
+constexpr int link_status(int own_status, uint32_t own_sig_set, uint32_t issuer, uint64_t n, int issuer_status, uint32_t issuer_key_set) {
+    if (own_status != ST_OK) return own_status;
+    if (issuer == NO_ISSUER) return ST_PARSE_ONLY;
+    return signer_status(own_status, own_sig_set, issuer, n, issuer_status, issuer_key_set);
 }
 
 // Byte idx of the two Name TLVs at blob positions a and b, both len bytes long: their difference, 0 behind the Names' end.  Here f

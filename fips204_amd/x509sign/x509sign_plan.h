@@ -25,7 +25,6 @@ using mldsa_rec::CLASS_87;
 using mldsa_rec::CLASS_REFUSED;
 using mldsa_rec::in_range;
 using mldsa_rec::sig_len;
-using mldsa_rec::up256;
 using mldsa_x509::oid_set;
 using mldsa_x509::OID_LEN;
 using mldsa_x509::read_tlv;
@@ -126,10 +125,11 @@ constexpr int walk_tbs(const Fetch& f, uint32_t len, uint32_t set) {
 }
 
 // ---- the working memory (include/mldsa_x509sign.h spells the formula out) -----------------------------------------------------------------
+// the placement scan's of ../rec/rec_plan.h under this library's block and cap: the sums of certificate lengths and accepted requests,
+// the lengths
 constexpr size_t MAX_CERTS = (size_t)1 << 30;
-constexpr size_t SUMS_PER_BLOCK = 2;  // the workgroup's sum of certificate lengths and its count of accepted requests
-constexpr size_t n_blocks(size_t n) { return (n + CHECK_BLOCK - 1) / CHECK_BLOCK; }
-constexpr size_t plan_sums_bytes(size_t n) { return up256(8 * SUMS_PER_BLOCK * n_blocks(n)); }
-constexpr size_t plan_bytes(size_t n) { return n > MAX_CERTS ? 0 : plan_sums_bytes(n) + up256(4 * n); }
+constexpr size_t n_blocks(size_t n) { return mldsa_rec::scan_blocks(n, CHECK_BLOCK); }
+constexpr size_t plan_sums_bytes(size_t n) { return mldsa_rec::place_sums_bytes(n, CHECK_BLOCK, mldsa_rec::PLACE_SUMS); }
+constexpr size_t plan_bytes(size_t n) { return mldsa_rec::place_plan_bytes(n, CHECK_BLOCK, MAX_CERTS); }
 
 }  // namespace mldsa_x509sign

@@ -170,6 +170,24 @@ static void edges() {
     CHECK(link_status(ST_OK, 44, 3, n, ST_DER, 44) == ST_ISSUER && link_status(ST_OK, 44, 3, n, ST_OK, 0) == ST_ISSUER);
     CHECK(link_status(ST_OK, 44, 3, n, ST_OK, 65) == ST_ISSUER && link_status(ST_OK, 44, 3, n, ST_ALG, 44) == ST_OK);
     CHECK(link_status(ST_OK, 87, 9, n, 7, 87) == ST_OK && link_status(ST_OK, 44, 0, 0, 0, 0) == ST_ISSUER);
+    // a CRL always names an issuer: 0xFFFFFFFF, the certificate's "no issuer", is out of range under every cap and never "parse only"
+    static_assert(MAX_CERTS == (size_t)1 << 30 && mldsa_x509::NO_ISSUER == 0xFFFFFFFFu && mldsa_x509::ST_PARSE_ONLY == 7, "the caps and the sentinel");
+    CHECK(link_status(ST_OK, 44, 0xFFFFFFFFu, (uint64_t)1 << 30, 0, 0) == ST_ISSUER && link_status(ST_OK, 44, 0xFFFFFFFFu, MAX_CERTS, ST_OK, 44) == ST_ISSUER);
+    CHECK(link_status(ST_OK, 44, (1u << 30) - 1, MAX_CERTS, ST_OK, 44) == ST_OK && link_status(ST_OK, 44, 1u << 30, MAX_CERTS, ST_OK, 44) == ST_ISSUER);
+    // same_alg, which walk_crl takes from the certificate's plan: a heap block of exactly the two contents, each byte in turn
+    {
+        uint8_t* block = static_cast<uint8_t*>(std::malloc(2 * OID_LEN));
+        const uint8_t oid[OID_LEN] = {0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x03, 0x12};
+        std::memcpy(block, oid, OID_LEN);
+        std::memcpy(block + OID_LEN, oid, OID_LEN);
+        CHECK(same_alg(Heap{block}, 0, OID_LEN));
+        for (uint32_t j = 0; j < OID_LEN; j++) {
+            block[j] ^= 0x40;
+            CHECK(!same_alg(Heap{block}, 0, OID_LEN) && !same_alg(Heap{block}, OID_LEN, 0));
+            block[j] ^= 0x40;
+        }
+        std::free(block);
+    }
     CHECK(answer(false, false, false, false, false, true) == REV_NO_CRL && answer(true, false, true, true, true, true) == REV_CRL_INDEX);
     CHECK(answer(true, true, false, false, false, true) == REV_CRL_REFUSED && answer(true, true, true, false, false, true) == REV_CERT);
     CHECK(answer(true, true, true, true, false, true) == REV_SCOPE && answer(true, true, true, true, true, true) == REV_REVOKED);

@@ -128,6 +128,17 @@ static void arithmetic() {
     CHECK(prefix_byte(2, 0x1234 + 4, 9) == 0x12 && prefix_byte(3, 0x1234 + 4, 9) == 0x34 && prefix_byte(10, 300, 9) == 9);
     CHECK(plan_bytes(0) == 0 && plan_bytes(1) == 512 && plan_bytes(256) == 256 + 1024 && plan_bytes(257) == 256 + 1280);
     CHECK(plan_bytes(MAX_REQUESTS) != 0 && plan_bytes(MAX_REQUESTS + 1) == 0);
+    CHECK(n_blocks(0) == 0 && n_blocks(256) == 1 && n_blocks(257) == 2 && plan_sums_bytes(16 * 256) == 256 && plan_sums_bytes(16 * 256 + 1) == 512);
+    // same_alg, which the walk takes from the certificate's plan: a heap block of exactly the two contents, each byte in turn
+    uint8_t* block = static_cast<uint8_t*>(std::malloc(2 * OID_LEN));
+    for (uint32_t j = 0; j < 2 * OID_LEN; j++) block[j] = (uint8_t)alg_byte(2 + j % OID_LEN, 1);
+    CHECK(same_alg(Heap{block}, 0, OID_LEN));
+    for (uint32_t j = 0; j < OID_LEN; j++) {
+        block[OID_LEN + j] ^= 0x01;
+        CHECK(!same_alg(Heap{block}, 0, OID_LEN) && !same_alg(Heap{block}, OID_LEN, 0));
+        block[OID_LEN + j] ^= 0x01;
+    }
+    std::free(block);
 }
 
 int main() {

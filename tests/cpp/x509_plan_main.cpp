@@ -208,8 +208,35 @@ static void tlv_edges() {
     CHECK(rd(b, 0, (uint32_t)b.size()).ok && rd(b, 0, (uint32_t)b.size()).len == 128 && !rd(b, 0, (uint32_t)b.size() - 1).ok);
 }
 
+// same_alg on a heap block of exactly the two contents: equal, and unequal in each of the OID_LEN bytes in turn, first and last included
+static void same_alg_edges() {
+    for (int c = 0; c < 3; c++) {
+        uint8_t* block = static_cast<uint8_t*>(std::malloc(2 * OID_LEN));
+        const uint8_t oid[OID_LEN] = {0x06, 0x09, 0x60, 0x86, 0x48, 0x01, 0x65, 0x03, 0x04, 0x03, (uint8_t)(0x11 + c)};
+        std::memcpy(block, oid, OID_LEN);
+        std::memcpy(block + OID_LEN, oid, OID_LEN);
+        const Heap f{block};
+        CHECK(same_alg(f, 0, OID_LEN) && same_alg(f, OID_LEN, 0) && same_alg(f, 0, 0) && same_alg(f, OID_LEN, OID_LEN));
+        for (uint32_t j = 0; j < OID_LEN; j++)
+            for (uint8_t flip : {0x01, 0x80, 0xFF}) {
+                block[OID_LEN + j] ^= flip;
+                CHECK(!same_alg(f, 0, OID_LEN) && !same_alg(f, OID_LEN, 0) && same_alg(f, OID_LEN, OID_LEN));
+                block[OID_LEN + j] ^= flip;
+            }
+        CHECK(same_alg(f, 0, OID_LEN));
+        std::free(block);
+    }
+}
+
 static void link_and_names() {
     const uint64_t n = 10;
+    // the rules a CRL shares: the certificate's without its "no issuer" case, at the caps' edge too
+    CHECK(signer_status(ST_OK, 44, NO_ISSUER, n, 0, 0) == ST_ISSUER && signer_status(ST_OK, 44, NO_ISSUER, (uint64_t)1 << 30, 0, 0) == ST_ISSUER);
+    CHECK(link_status(ST_OK, 44, NO_ISSUER, (uint64_t)1 << 30, 0, 0) == ST_PARSE_ONLY && signer_status(ST_SIG, 0, NO_ISSUER, n, 0, 0) == ST_SIG);
+    for (uint32_t issuer : {0u, 3u, 9u, 10u, 0xFFFFFFFEu})
+        for (int ist : {ST_OK, ST_RANGE, ST_DER, ST_ALG, ST_PARSE_ONLY})
+            for (uint32_t ks : {0u, 44u, 65u})
+                for (int own : {ST_OK, ST_DER, ST_SIG}) CHECK(signer_status(own, 44, issuer, n, ist, ks) == link_status(own, 44, issuer, n, ist, ks));
     CHECK(link_status(ST_DER, 0, 3, n, ST_OK, 44) == ST_DER && link_status(ST_SIG, 0, NO_ISSUER, n, 0, 0) == ST_SIG);
     CHECK(link_status(ST_OK, 44, NO_ISSUER, n, 0, 0) == ST_PARSE_ONLY && link_status(ST_OK, 44, 10, n, 0, 0) == ST_ISSUER);
     CHECK(link_status(ST_OK, 44, 0xFFFFFFFEu, n, 0, 0) == ST_ISSUER);
@@ -239,6 +266,7 @@ static void link_and_names() {
 int main() {
     for (int set : {44, 65, 87}) one_set(set);
     tlv_edges();
+    same_alg_edges();
     link_and_names();
     if (g_fail) {
         std::fprintf(stderr, "%d checks failed\n", g_fail);

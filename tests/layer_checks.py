@@ -196,25 +196,93 @@ def sources_clean(layer_dir, extra_files, asm_free=True):
     return read
 
 
-def shared_plan_is_shared_once(src, scan, host, makefile, scan_h, host_h):
-    """The record libraries' plan (fips204_amd/rec/rec_scan.h, rec_host.h) is used by the library's .hip `src`, not restated in it:
-    `src` includes both headers under the names `scan_h` and `host_h`, its Makefile names them, the scan's LDS and every shared
-    definition are in the headers alone, and the headers give everything internal linkage."""
+def shared_plan_is_shared_once(src, scan, wave, host, makefile, scan_h, wave_h, host_h):
+    """The record libraries' plan (fips204_amd/rec/rec_scan.h with rec_wave.h, rec_host.h) is used by the library's .hip `src`, not
+    restated in it: `src` includes the scan and the host header under the names `scan_h` and `host_h`, the scan includes the wave
+    helpers, the library's Makefile names all three, the scan's LDS and every shared definition are in the headers alone, and the
+    headers give everything internal linkage."""
     for h in (scan_h, host_h):
         assert f'#include "{h}"' in src and h in makefile, h  # a change of a shared header rebuilds the library
+    assert '#include "rec_wave.h"' in scan and wave_h in makefile and '#include "rec_scan.h"' not in wave
     # LDS: the per-wave partial sums of the two scan kernels only
-    assert scan.count("__shared__") == 2 and "__shared__" not in src + host and "extern __shared__" not in scan
+    assert scan.count("__shared__") == 2 and "__shared__" not in src + host + wave and "extern __shared__" not in scan
     for name in ("op_values", "wave_inclusive", "copy_field", "k_classify", "k_offsets", "k_apply", "plan_layout", "front_layout",
                  "check_plan_memory", "launch_plan", "totals_consistent", "read_totals"):
         defined = r"^[^\n;=/]*\b(void|bool|int|uint64_t|size_t)\s+%s\s*\(" % name
         assert not re.search(defined, src, flags=re.M), name
-        assert len(re.findall(defined, scan + host, flags=re.M)) == 1, name
+        assert len(re.findall(defined, scan + wave + host, flags=re.M)) == 1, name
+    for name in ("wave_inclusive", "copy_field"):  # the two that the certificate layers take too: in the header without kernels
+        assert re.search(r"\b(void|uint64_t)\s+%s\s*\(" % name, wave), name
     for word in ("SCAN_WAVES =", "SLOT_MASK =", "struct PlanLayout", "struct FrontLayout"):
-        assert word not in src and (scan + host).count(word) == 1, word
-    for text in (scan, host):  # layer_host.h's style: two libraries in one process share no kernel stub and no function
+        assert word not in src and (scan + wave + host).count(word) == 1, word
+    for text in (scan, wave, host):  # layer_host.h's style: two libraries in one process share no kernel stub and no function
         assert re.search(r"\nnamespace mldsa_rec \{\nnamespace \{\n", text) and text.rstrip().endswith("}  // namespace\n}  // namespace mldsa_rec")
         assert not re.search(r"\bextern\b", text)
-    assert "__global__" not in host and "hipLaunchKernelGGL" not in scan  # device code in one header, host code in the other
+    assert "__global__" not in host + wave and "hipLaunchKernelGGL" not in scan + wave  # device code in two headers, host code in the third
+
+
+# ---- what the certificate layers share (x509, x509sign, csr, crl, path, find) -------------------------------------------------------
+CERT_LAYERS = ("x509", "x509sign", "csr", "crl", "path", "find")
+# helper -> the one file that defines it (relative to fips204_amd/); the pattern of its definition is SHARED_DEFINED % name
+CERT_SHARED = {
+    "BlobBytes": "x509/x509_dev.h", "wave_names_differ": "x509/x509_dev.h", "write_link_op": "x509/x509_dev.h",
+    "place_block_sums": "rec/rec_place.h", "place_block_offsets": "rec/rec_place.h", "place_wave_scan": "rec/rec_place.h",
+    "place_before": "rec/rec_place.h", "place_totals": "rec/rec_place.h", "place_fits": "rec/rec_place.h",
+    "wave_sum": "layer/layer_dev.h",
+    "same_alg": "x509/x509_plan.h", "ranges_apart": "layer/layer_host.h",
+    "scan_blocks": "rec/rec_plan.h", "place_sums_bytes": "rec/rec_plan.h", "place_plan_bytes": "rec/rec_plan.h",
+}
+SHARED_DEFINED = r"^[^\n;=/(]*\b(?:struct\s+%s\s*\{|(?:void|bool|int|uint32_t|uint64_t|size_t)\s+%s\s*\()"
+# Pieces that did not pass the rule of layer_dev.h ("the same instructions as written out") and so are defined nowhere: they stay
+# written out in the kernels and walks that use them, and the headers and DESIGN.md say why.
+#   signed_envelope, alg_sig  as functions of x509_plan.h they change the registers of k_x509_parse, k_crl_parse and k_csr_parse
+#   name_ranges               lane 0's decision on the two Name ranges in k_x509_link and k_crl_link, and the broadcast behind it
+#   (k_crl_place keeps its scan written out too: with the placement helpers it takes two more VGPRs)
+CERT_NOT_SHARED = ("signed_envelope", "alg_sig", "name_ranges")
+CERT_NEW_HEADERS = {"x509/x509_dev.h": "mldsa_x509", "rec/rec_place.h": "mldsa_rec", "rec/rec_wave.h": "mldsa_rec"}
+
+
+def certificate_helpers_shared_once(layer):
+    """What the certificate layers share is defined exactly once in the tree and in none of their .hip files; the .hip of `layer` that
+    uses a helper includes its header (directly, or for the plan headers through its own plan header) and its Makefile names it; the
+    new headers keep everything in an unnamed namespace inside their named one and hold no kernel and no `extern`."""
+    base = os.path.join(ROOT, "fips204_amd")
+    tree = {}
+    for path in glob.glob(os.path.join(base, "**", "*"), recursive=True):
+        if path.endswith((".h", ".hip", ".cpp", ".hpp")):
+            tree[os.path.relpath(path, base)] = open(path, errors="replace").read()
+    hips = ["%s/%s.hip" % (l, l) for l in CERT_LAYERS]
+    for name, home in CERT_SHARED.items():
+        pat = SHARED_DEFINED % (name, name)
+        where = sorted(f for f, text in tree.items() if re.search(pat, text, flags=re.M))
+        assert where == [home], (name, where)
+        assert len(re.findall(pat, tree[home], flags=re.M)) == 1, name
+    for name in ("wave_inclusive", "copy_field"):  # rec_wave.h's (shared_plan_is_shared_once counts them among the record headers)
+        assert not any(re.search(SHARED_DEFINED % (name, name), tree[f], flags=re.M) for f in hips), name
+    for name in CERT_NOT_SHARED:
+        assert not any(re.search(SHARED_DEFINED % (name, name), text, flags=re.M) for text in tree.values()), name
+    assert set(hips) <= set(tree)
+    src, mk = tree["%s/%s.hip" % (layer, layer)], open(os.path.join(base, layer, "Makefile")).read()
+    code = re.sub(r"//[^\n]*", "", src)
+    plan = tree["%s/%s_plan.h" % (layer, layer)]
+    used = 0
+    for name, home in CERT_SHARED.items():
+        if not re.search(r"\b%s\b" % name, code + re.sub(r"//[^\n]*", "", plan)):
+            continue
+        used += 1
+        rel = os.path.basename(home) if home.startswith(layer + "/") else "../" + home
+        assert rel in mk, (layer, name, rel)  # a change of the shared header rebuilds the library
+        reached = [src, plan] + [tree[h] for h in CERT_NEW_HEADERS] + [tree["x509/x509_plan.h"], tree["x509sign/x509sign_plan.h"]]
+        assert any('#include "%s"' % inc in text for text in reached for inc in (rel, os.path.basename(home), "../" + home)), (layer, name)
+    assert used >= 1, layer  # BlobBytes at the least
+    assert '#include "%s"' % ("x509_dev.h" if layer == "x509" else "../x509/x509_dev.h") in src
+    assert "rec_scan.h" not in src + mk  # the class scan's kernels are the record libraries' alone
+    for h, ns in CERT_NEW_HEADERS.items():
+        text = tree[h]
+        assert re.search(r"\nnamespace %s \{\nnamespace \{\n" % ns, text) and text.rstrip().endswith("}  // namespace\n}  // namespace " + ns), h
+        body = re.sub(r"//[^\n]*", "", text)  # (the comments say what stays in the kernels)
+        assert "__global__" not in body and "__shared__" not in body and not re.search(r"\bextern\b", body), h
+        assert "hipLaunchKernelGGL" not in body and "#pragma once" in body, h
 
 
 # what libmldsa_rec.so and libmldsa_recsign.so exported beside their entry points before the plan was shared: libstdc++'s inline functions

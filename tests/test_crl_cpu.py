@@ -13,7 +13,7 @@ import pytest
 import crl_cases as cc
 import x509_cases as xc
 from fips204_amd import _crl_lib, _csr_lib, _lib, _mus_lib, _x509_lib, _x509sign_lib
-from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
+from layer_checks import (ROOT, certificate_helpers_shared_once, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
                           links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program, sources_clean)
 from oracle import oracle as orc
 
@@ -45,7 +45,8 @@ def test_clean_build_in_a_shadow_tree(lib, tmp_path):
     clean_build("crl", _crl_lib, SOURCES, libs, tmp_path)
     mk = open(os.path.join(CRL_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    for h in ("../x509/x509_plan.h", "../rec/rec_plan.h", "../rec/rec_scan.h", "crl_plan.h", "mldsa_crl.h", "mldsa_x509.h", "mldsa_rec.h"):
+    for h in ("../x509/x509_plan.h", "../x509/x509_dev.h", "../rec/rec_plan.h", "../rec/rec_wave.h", "../rec/rec_place.h", "crl_plan.h", "mldsa_crl.h",
+              "mldsa_x509.h", "mldsa_rec.h"):
         assert h in mk, h  # a change of a shared header rebuilds this library
     assert not re.search(r"-lmldsa_(rec|recsign|x509|x509sign|csr)\b", mk)
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
@@ -122,9 +123,11 @@ def test_kernels_do_not_spill_and_sources_are_clean(lib):
     for stem in KERNELS:
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) == len(KERNELS)
-    read = dict(sources_clean(CRL_DIR, ["../../include/mldsa_crl.h", "../_crl_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]))
-    src, plan = read["crl.hip"], read["crl_plan.h"]
-    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../../include/mldsa_crl.h", "../rec/rec_scan.h", "crl_plan.h"):
+    read = dict(sources_clean(CRL_DIR, ["../../include/mldsa_crl.h", "../_crl_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h",
+                                        "../rec/rec_place.h", "../x509/x509_dev.h"]))
+    src, plan, shared = read["crl.hip"], read["crl_plan.h"], read["../rec/rec_place.h"] + read["../x509/x509_dev.h"]
+    certificate_helpers_shared_once("crl")
+    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../../include/mldsa_crl.h", "../rec/rec_place.h", "../x509/x509_dev.h", "crl_plan.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../x509/x509_plan.h"' in plan
     # no wave waits for another, no host wait; the scaffold and the shared walks are included, not copied
@@ -137,7 +140,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(lib):
     # the plan has no HIP in it, and the kernels keep no second copy of its rules: they call the plan's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
-    kernel_code = re.sub(r"//[^\n]*", "", src)
+    kernel_code = re.sub(r"//[^\n]*", "", src + shared)  # (the placement scan and the link step's comparison are shared with other layers)
     for call in ("walk_crl(", "walk_entry(", "hop(", "load_serial(", "cert_serial(", "hash_serial(", "link_status(", "place_status(", "answer(",
                  "window_at(", "window_chunk(", "window_holds(", "entries_bound(", "name_byte_diff(", "in_range(", "wave_or(", "wave_inclusive("):
         assert call in kernel_code and "constexpr" in plan, call

@@ -15,7 +15,7 @@ import csr_cases as cs
 import x509_cases as xc
 import x509sign_cases as xs
 from fips204_amd import _csr_lib, _lib, _mus_lib, _x509_lib, _x509sign_lib
-from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
+from layer_checks import (ROOT, certificate_helpers_shared_once, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
                           links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program)
 from oracle import oracle as orc
 
@@ -47,7 +47,8 @@ def test_clean_build_in_a_shadow_tree(lib, tmp_path):
     clean_build("csr", _csr_lib, SOURCES, libs, tmp_path)
     mk = open(os.path.join(CSR_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    for h in ("../x509/x509_plan.h", "../x509sign/x509sign_plan.h", "../rec/rec_plan.h", "../rec/rec_scan.h", "csr_plan.h", "mldsa_csr.h"):
+    for h in ("../x509/x509_plan.h", "../x509/x509_dev.h", "../x509sign/x509sign_plan.h", "../rec/rec_plan.h", "../rec/rec_wave.h", "../rec/rec_place.h",
+              "csr_plan.h", "mldsa_csr.h"):
         assert h in mk, h  # a change of a shared header rebuilds this library
     assert not re.search(r"-lmldsa_(rec|recsign|x509|x509sign)\b", mk)
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
@@ -215,8 +216,8 @@ def test_kernels_do_not_spill(lib):
     kernels = kernel_resources(CSR_DIR)
     for stem in KERNELS:
         assert sum(stem in nm for nm in kernels) == 1, stem
-    # rec_scan.h's one kernel that is no template comes along with the header; its class-scan templates are not instantiated
-    assert sorted(nm for nm in kernels if not any(stem in nm for stem in KERNELS)) == ["_ZN9mldsa_rec12_GLOBAL__N_19k_offsetsEPmjS1_"]
+    assert len(kernels) == len(KERNELS)  # rec_wave.h and rec_place.h bring no kernel along: nothing is compiled that is not launched
+    certificate_helpers_shared_once("csr")
     # LDS in the scan alone: the walk and the write use none
     res = open(os.path.join(CSR_DIR, "csr.res")).read()
     lds = dict(zip(re.findall(r"Function Name: (\S+)", res), (int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", res))))

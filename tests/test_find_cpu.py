@@ -16,7 +16,7 @@ import find_cases as fc
 import path_cases as pc
 import x509_cases as xc
 from fips204_amd import _crl_lib, _find_lib, _lib, _mus_lib, _path_lib, _x509_lib
-from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
+from layer_checks import (ROOT, certificate_helpers_shared_once, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
                           links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program, sources_clean)
 
 FIND_DIR = os.path.join(ROOT, "fips204_amd", "find")
@@ -47,7 +47,7 @@ def test_clean_build_in_a_shadow_tree(lib, tmp_path):
     clean_build("find", _find_lib, SOURCES, libs, tmp_path)
     mk = open(os.path.join(FIND_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    for h in ("../x509/x509_plan.h", "../rec/rec_plan.h", "find_plan.h", "mldsa_find.h", "mldsa_path.h", "mldsa_crl.h", "mldsa_x509.h", "mldsa_rec.h"):
+    for h in ("../x509/x509_plan.h", "../x509/x509_dev.h", "../rec/rec_plan.h", "find_plan.h", "mldsa_find.h", "mldsa_path.h", "mldsa_crl.h", "mldsa_x509.h", "mldsa_rec.h"):
         assert h in mk, h  # a change of a shared header rebuilds this library
     assert not re.search(r"-lmldsa_(rec|recsign|x509|x509sign|csr|crl|path)\b", mk)
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
@@ -117,7 +117,8 @@ def test_kernels_do_not_spill_and_sources_are_clean(lib):
     assert len(kernels) == len(KERNELS)
     read = dict(sources_clean(FIND_DIR, ["../../include/mldsa_find.h", "../_find_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]))
     src, plan = read["find.hip"], read["find_plan.h"]
-    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../../include/mldsa_find.h", "find_plan.h"):
+    certificate_helpers_shared_once("find")
+    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../x509/x509_dev.h", "../../include/mldsa_find.h", "find_plan.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../x509/x509_plan.h"' in plan and '#include "../rec/rec_plan.h"' in open(os.path.join(FIND_DIR, "..", "x509", "x509_plan.h")).read()
     # no wave waits for another, no host wait, no allocation; the scaffold and the shared readers are included, not copied

@@ -109,6 +109,31 @@ def test_mixed_sets_match_the_restatement_byte_for_byte(rl, n):
     assert (f[n * 88:] == CANARY).all() and np.array_equal(f[:n * 88].view(_crl_lib.FIELDS_DTYPE), cc.expected_parse(blob, items))
 
 
+CARRY_N = 64 * 256 + 1  # 65 workgroups of the scan: the one-wave offsets kernel goes round its carry loop a second time
+CARRY_AT = (0, 255, 256, 16127, 16128, 16383, 16384)  # the accepted few: both ends of the first and the 64th workgroup, and the 65th
+
+
+def test_placement_scan_carries_past_64_workgroups(rl):
+    """16 385 CRLs of which seven are accepted; every other one is a RANGE refusal (no length, or an offset behind the blob's end), so
+    the blob stays seven CRLs long.  Then the same with one slot too few: the first CRL whose slots do not fit is the one behind the
+    carry."""
+    crls = [cc.random_crl(cc.SETS[j % 3], cc.CA_CN[cc.SETS[j % 3]], b"carry", j, 2 + j) for j in range(len(CARRY_AT))]
+    blob, certs, few, cert_fields = cc.lay_out(cc.ca_certs(), [0, 1, 2], [(d, len(d)) for d in crls], [j % 3 for j in range(len(crls))],
+                                               pad=[0, 5, 11, 2], front=1)
+    items = np.zeros(CARRY_N, dtype=few.dtype)
+    items["off"][1::2], items["len"][1::2] = blob.size + 1, 100  # behind the end; the even ones have no length
+    items[list(CARRY_AT)] = few
+    need = int(cc.expected(blob, items, cert_fields, cc.max_entries_of(few))[4][0]["slots"])  # the sum of the seven bounds
+    d, want = ops_match(rl, (blob, certs, items, cert_fields), max_entries=need, shift=1)
+    fields, entries, ops, status, totals = want
+    assert np.nonzero(status == cc.OK)[0].tolist() == list(CARRY_AT) and (status == cc.RANGE).sum() == CARRY_N - len(CARRY_AT)
+    assert fields["count"][list(CARRY_AT)].tolist() == [2 + j for j in range(len(CARRY_AT))]
+    assert int(fields[CARRY_AT[-1]]["first"]) == need - int(fields[CARRY_AT[-1]]["revoked_len"]) // cc.ENTRY_MIN > 20
+    assert (int(totals[0]["accepted"]), int(totals[0]["refused"]), int(totals[0]["slots"])) == (len(CARRY_AT), CARRY_N - len(CARRY_AT), need)
+    d, want = ops_match(rl, (blob, certs, items, cert_fields), max_entries=need - 1, shift=1)
+    assert np.nonzero(want[3] == cc.SPACE)[0].tolist() == [CARRY_AT[-1]] and int(want[4][0]["accepted"]) == len(CARRY_AT) - 1
+
+
 @pytest.mark.parametrize("shift", (0, 1, 7, 15))
 def test_entry_counts_at_the_wave_seam_and_two_window_reloads(rl, shift):
     cas = cc.ca_certs()

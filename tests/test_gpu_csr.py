@@ -118,6 +118,34 @@ def test_both_stages_match_the_restatement_byte_for_byte(front, n, mix):
         seam(front, batch, shift=2, out_shift=9, split=True)
 
 
+CARRY_N = 64 * 256 + 1  # 65 workgroups of the scan: the one-wave offsets kernel goes round its carry loop a second time
+CARRY_AT = (0, 255, 256, 16127, 16128, 16383, 16384)  # the accepted few: both ends of the first and the 64th workgroup, and the 65th
+
+
+def test_placement_scan_carries_past_64_workgroups(front):
+    """stage 2 over 16 385 rows of which seven are accepted; every other one is refused for its verdict (ok = 0: POP), so the blob stays
+    seven requests long.  Then the same with one byte too few: the first TBSCertificate that does not fit is the one behind the carry,
+    and it corrects the totals."""
+    small = cs.seam_case(len(CARRY_AT), "mod3", seed=4, front=1)
+    assert not small["parse"][2].any()
+    fields = np.zeros(CARRY_N, dtype=small["fields"].dtype)
+    entries = np.zeros(CARRY_N, dtype=small["entries"].dtype)
+    ok = np.zeros(CARRY_N, dtype=np.uint8)
+    entries["set"], entries["serial_len"] = 44, 1
+    fields[list(CARRY_AT)], entries[list(CARRY_AT)], ok[list(CARRY_AT)] = small["fields"], small["entries"], 1
+    _, blob_d, _ = placed(small["blob"], 3)
+    free = cs.expected_tbs(small["blob"], fields, entries, ok, 2 ** 62)
+    need = free["totals"][2]
+    assert np.nonzero(free["status"] == cs.OK)[0].tolist() == list(CARRY_AT) and (free["status"] == cs.POP).sum() == CARRY_N - len(CARRY_AT)
+    assert free["totals"] == (len(CARRY_AT), CARRY_N - len(CARRY_AT), need)
+    for out_len in (need, need - 1):
+        want = cs.expected_tbs(small["blob"], fields, entries, ok, out_len)
+        got = run_tbs(front, blob_d, fields, entries, ok, out_len, out_shift=5)
+        check_tbs(got, want, out_len)
+    assert np.nonzero(want["status"] == cs.SPACE)[0].tolist() == [CARRY_AT[-1]]
+    assert got["totals"] == (len(CARRY_AT) - 1, CARRY_N - len(CARRY_AT) + 1, need)
+
+
 def test_every_defect_of_both_stages_among_valid_neighbours(front):
     batch, at = cs.defect_batch()
     got, want = seam(front, batch, shift=3, out_shift=1)

@@ -114,6 +114,30 @@ def test_seam_matches_the_restatement_byte_for_byte(issuer, n, mix):
         check_seam(run_seam(issuer, blob, reqs, out_len, shift=2, out_shift=9, split=True), xs.expected(blob, reqs, xs.N_KEYS, out_len), out_len)
 
 
+CARRY_N = 64 * 256 + 1  # 65 workgroups of the scan: the one-wave offsets kernel goes round its carry loop a second time
+CARRY_AT = (0, 255, 256, 16127, 16128, 16383, 16384)  # the accepted few: both ends of the first and the 64th workgroup, and the 65th
+
+
+def test_placement_scan_carries_past_64_workgroups(issuer):
+    """16 385 requests of which seven are accepted; every other one is a RANGE refusal (no length, or an offset behind the blob's end),
+    so the blob stays seven TBSs long.  Then the same with one byte too few: the first certificate that does not fit is the one behind
+    the carry, and it corrects the totals."""
+    tbss = [xs.good_tbs(xs.SETS[j % 3], b"carry", j, tail=xc.extensions(3 * j)) for j in range(len(CARRY_AT))]
+    blob, few = xs.lay_out([(xs.SETS[j % 3], j % 4, t, len(t), xc._bytes(b"crnd", j, 32) if j % 2 else None, j) for j, t in enumerate(tbss)],
+                           pad=[0, 3, 8, 13, 5], front=1)
+    reqs = np.zeros(CARRY_N, dtype=few.dtype)
+    reqs["set"], reqs["key"], reqs["issuer"] = 44, 1, xs.NO_ISSUER
+    reqs["off"][1::2], reqs["len"][1::2] = blob.size + 1, 100  # behind the end; the even ones have no length
+    reqs[list(CARRY_AT)] = few
+    got, want = seam(issuer, blob, reqs, shift=1, out_shift=3)
+    assert np.nonzero(want["status"] == xs.OK)[0].tolist() == list(CARRY_AT) and (want["status"] == xs.RANGE).sum() == CARRY_N - len(CARRY_AT)
+    need = want["totals"][2]
+    assert want["totals"] == (len(CARRY_AT), CARRY_N - len(CARRY_AT), need) and int(got["out_certs"][CARRY_AT[-1]]["off"]) > 6 * 2400
+    got, short = seam(issuer, blob, reqs, out_len=need - 1, shift=1, out_shift=3)
+    assert np.nonzero(short["status"] == xs.SPACE)[0].tolist() == [CARRY_AT[-1]]
+    assert got["totals"] == (len(CARRY_AT) - 1, CARRY_N - len(CARRY_AT) + 1, need)
+
+
 def test_every_defect_among_valid_neighbours(issuer):
     blob, reqs, at = xs.defect_batch()
     got, want = seam(issuer, blob, reqs, shift=3, out_shift=1)

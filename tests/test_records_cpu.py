@@ -18,7 +18,7 @@ from layer_checks import (PK_SK, ROOT, aligned_buffer, built, clean_build, core_
 from oracle import oracle as orc
 
 REC_DIR = os.path.join(ROOT, "fips204_amd", "rec")
-SOURCES = ["Makefile", "rec.hip", "rec_plan.h", "rec_scan.h", "rec_host.h"]
+SOURCES = ["Makefile", "rec.hip", "rec_plan.h", "rec_scan.h", "rec_wave.h", "rec_host.h"]
 
 
 @pytest.fixture(scope="module")
@@ -191,20 +191,20 @@ def test_kernels_do_not_spill_and_sources_are_clean(rec):
     assert len(kernels) == 5
     # sources_clean reads the whole directory: rec_scan.h and rec_host.h, which libmldsa_recsign.so shares, are among its files
     read = dict(sources_clean(REC_DIR, ["../../include/mldsa_rec.h", "../_rec_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]))
-    src, plan, scan, host = read["rec.hip"], read["rec_plan.h"], read["rec_scan.h"], read["rec_host.h"]
+    src, plan, scan, wave, host = read["rec.hip"], read["rec_plan.h"], read["rec_scan.h"], read["rec_wave.h"], read["rec_host.h"]
     for h in ("../layer/layer_host.h", "../../include/mldsa_rec.h", "rec_plan.h", "rec_scan.h", "rec_host.h"):
         assert f'#include "{h}"' in src, h
     # the kernel boundaries do the ordering: no atomics, no flag another workgroup waits for, no spin loop; the scaffold is shared, not copied
     for word in ("atomic", "__threadfence", "while (true)", "for (;;)", "s_sleep", "hipGraph", "hipStreamCreate", "struct DeviceScope",
                  "thread_local", "int fail("):
-        assert word not in src + plan + scan + host, word
-    shared_plan_is_shared_once(src, scan, host, open(os.path.join(REC_DIR, "Makefile")).read(), "rec_scan.h", "rec_host.h")
+        assert word not in src + plan + scan + wave + host, word
+    shared_plan_is_shared_once(src, scan, wave, host, open(os.path.join(REC_DIR, "Makefile")).read(), "rec_scan.h", "rec_wave.h", "rec_host.h")
     no_new_dynamic_symbol(_rec_lib.LIB_PATH, "mldsa_rec_")
     # the plan has no HIP in it, and the kernel keeps no second copy of its arithmetic: it calls the plan's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
     own_code = re.sub(r"//[^\n]*", "", src)
-    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan)
+    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan + wave)
     for call in ("copy_plan(", "chunk_src(", "funnel16(", "classify(", "in_range("):
         assert call in kernel_code and "constexpr" in plan, call
     for name in ("copy_plan", "chunk_src", "funnel16", "funnel_at", "in_range", "sig_len", "class_of_set", "up256"):

@@ -40,7 +40,7 @@ def test_clean_build_in_a_shadow_tree(recsign, tmp_path):
     clean_build("recsign", _recsign_lib, SOURCES, libs, tmp_path)  # build() builds it: the library is there after build()
     mk = open(os.path.join(RECSIGN_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    for h in ("../rec/rec_plan.h", "../rec/rec_scan.h", "../rec/rec_host.h"):
+    for h in ("../rec/rec_plan.h", "../rec/rec_scan.h", "../rec/rec_wave.h", "../rec/rec_host.h"):
         assert h in mk, h  # a change of the shared plan rebuilds this library
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "_recsign_lib.load()" in entry  # build() loads the library it built
@@ -252,24 +252,26 @@ def test_kernels_do_not_spill_and_sources_are_clean(recsign):
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) == 5
     read = dict(sources_clean(RECSIGN_DIR, ["../../include/mldsa_recsign.h", "../_recsign_lib.py", "../layer/layer_host.h", "../rec/rec_plan.h",
-                                            "../rec/rec_scan.h", "../rec/rec_host.h"]))
+                                            "../rec/rec_scan.h", "../rec/rec_wave.h", "../rec/rec_host.h"]))
     src, plan, scan, host = read["recsign.hip"], read["recsign_plan.h"], read["../rec/rec_scan.h"], read["../rec/rec_host.h"]
+    wave = read["../rec/rec_wave.h"]
     for h in ("../layer/layer_host.h", "../../include/mldsa_recsign.h", "recsign_plan.h", "../rec/rec_scan.h", "../rec/rec_host.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../rec/rec_plan.h"' in plan and '#include "rec_plan.h"' not in src and "namespace mldsa_rec " not in src + plan
     # the kernel boundaries do the ordering: no atomics, no flag another workgroup waits for, no spin loop; the scaffold is shared, not copied
     for word in ("atomic", "__threadfence", "while (true)", "for (;;)", "s_sleep", "hipGraph", "hipStreamCreate", "struct DeviceScope",
                  "thread_local", "int fail(", "getenv", "printf"):
-        assert word not in src + plan + scan + host, word
-    assert not re.search(r"\basm\b", src + plan + scan + host)
+        assert word not in src + plan + scan + wave + host, word
+    assert not re.search(r"\basm\b", src + plan + scan + wave + host)
     # LDS (the per-wave partial sums of the two scan kernels only), the definitions and the includes of the shared plan
-    shared_plan_is_shared_once(src, scan, host, open(os.path.join(RECSIGN_DIR, "Makefile")).read(), "../rec/rec_scan.h", "../rec/rec_host.h")
+    shared_plan_is_shared_once(src, scan, wave, host, open(os.path.join(RECSIGN_DIR, "Makefile")).read(), "../rec/rec_scan.h", "../rec/rec_wave.h",
+                               "../rec/rec_host.h")
     no_new_dynamic_symbol(_recsign_lib.LIB_PATH, "mldsa_recsign_")
     # the plan has no HIP in it, and neither file keeps a second copy of the shared arithmetic: they call rec_plan.h's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
     own_code = re.sub(r"//[^\n]*", "", src)
-    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan)
+    kernel_code = own_code + re.sub(r"//[^\n]*", "", scan + wave)
     for call in ("copy_plan(", "chunk_src(", "funnel16(", "check_op(", "in_range("):
         assert call in kernel_code and "constexpr" in plan, call
     host_code = own_code + re.sub(r"//[^\n]*", "", host)

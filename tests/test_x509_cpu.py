@@ -12,12 +12,12 @@ import pytest
 
 import x509_cases as xc
 from fips204_amd import _lib, _mus_lib, _x509_lib
-from layer_checks import (PK_SK, ROOT, aligned_buffer, built, clean_build, core_params, header_and_exports, kernel_resources, layered_on_core,
+from layer_checks import (PK_SK, ROOT, certificate_helpers_shared_once, aligned_buffer, built, clean_build, core_params, header_and_exports, kernel_resources, layered_on_core,
                           links_the_core_and_never_builds_it, sanitized_program, sources_clean)
 from oracle import oracle as orc
 
 X509_DIR = os.path.join(ROOT, "fips204_amd", "x509")
-SOURCES = ["Makefile", "x509.hip", "x509_plan.h"]
+SOURCES = ["Makefile", "x509.hip", "x509_plan.h", "x509_dev.h"]
 
 
 @pytest.fixture(scope="module")
@@ -153,8 +153,9 @@ def test_kernels_do_not_spill_and_sources_are_clean(x509):
         assert sum(stem in nm for nm in kernels) == 1, stem
     assert len(kernels) == 2
     read = dict(sources_clean(X509_DIR, ["../../include/mldsa_x509.h", "../_x509_lib.py", "../layer/layer_host.h", "../layer/layer_dev.h"]))
-    src, plan = read["x509.hip"], read["x509_plan.h"]
-    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../../include/mldsa_x509.h", "x509_plan.h"):
+    src, plan, dev = read["x509.hip"], read["x509_plan.h"], read["x509_dev.h"]
+    certificate_helpers_shared_once("x509")
+    for h in ("../layer/layer_host.h", "../layer/layer_dev.h", "../../include/mldsa_x509.h", "x509_plan.h", "x509_dev.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../rec/rec_plan.h"' in plan
     # the kernel boundary does the ordering: no atomics, no flag another workgroup waits for, no host wait; the scaffold is shared, not copied
@@ -164,7 +165,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(x509):
     # the plan has no HIP in it, and the kernels keep no second copy of its rules: they call the plan's functions
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan
-    kernel_code = re.sub(r"//[^\n]*", "", src)
+    kernel_code = re.sub(r"//[^\n]*", "", src + dev)  # (the link step's comparison is x509_dev.h's, which k_crl_link shares)
     for call in ("walk(", "link_status(", "name_byte_diff(", "in_range(", "wave_or("):
         assert call in kernel_code and "constexpr" in plan, call
     for word in ("read_tlv", "0x1F", "0x80", "0x84", "0x30", "0x03", "0xA0", "0x0365014886600906"):  # the rules live in the plan alone

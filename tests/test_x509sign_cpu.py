@@ -14,7 +14,7 @@ import pytest
 import x509_cases as xc
 import x509sign_cases as xs
 from fips204_amd import _lib, _mus_lib, _recsign_lib, _x509_lib, _x509sign_lib
-from layer_checks import (ROOT, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
+from layer_checks import (ROOT, certificate_helpers_shared_once, aligned_buffer, built, clean_build, header_and_exports, kernel_resources, layered_on_core,
                           links_the_core_and_never_builds_it, no_new_dynamic_symbol, sanitized_program, sources_clean)
 from oracle import oracle as orc
 
@@ -44,7 +44,7 @@ def test_clean_build_in_a_shadow_tree(lib, tmp_path):
     clean_build("x509sign", _x509sign_lib, SOURCES, libs, tmp_path)
     mk = open(os.path.join(X509SIGN_DIR, "Makefile")).read()
     assert "include ../layer/layer.mk" in mk and "$(HIPCC)" not in mk and "clean" not in mk  # LIB, OBJS, HDRS and the shared recipe
-    for h in ("../x509/x509_plan.h", "../rec/rec_plan.h", "../rec/rec_scan.h", "x509sign_plan.h"):
+    for h in ("../x509/x509_plan.h", "../x509/x509_dev.h", "../rec/rec_plan.h", "../rec/rec_wave.h", "../rec/rec_place.h", "x509sign_plan.h"):
         assert h in mk, h  # a change of a shared header rebuilds this library
     assert not re.search(r"-lmldsa_(rec|recsign|x509)\b", mk)
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
@@ -204,12 +204,13 @@ def test_kernels_do_not_spill_and_sources_are_clean(lib):
     kernels = kernel_resources(X509SIGN_DIR)
     for stem in KERNELS:
         assert sum(stem in nm for nm in kernels) == 1, stem
-    # rec_scan.h's one kernel that is no template comes along with the header; its class-scan templates are not instantiated
-    assert sorted(nm for nm in kernels if not any(stem in nm for stem in KERNELS)) == ["_ZN9mldsa_rec12_GLOBAL__N_19k_offsetsEPmjS1_"]
+    assert len(kernels) == len(KERNELS)  # rec_wave.h and rec_place.h bring no kernel along: nothing is compiled that is not launched
     assert not any("k_classify" in nm or "k_apply" in nm for nm in kernels)
-    read = dict(sources_clean(X509SIGN_DIR, ["../../include/mldsa_x509sign.h", "../_x509sign_lib.py", "../layer/layer_host.h", "../rec/rec_scan.h"]))
-    src, plan = read["x509sign.hip"], read["x509sign_plan.h"]
-    for h in ("../layer/layer_host.h", "../rec/rec_scan.h", "../../include/mldsa_x509sign.h", "x509sign_plan.h"):
+    read = dict(sources_clean(X509SIGN_DIR, ["../../include/mldsa_x509sign.h", "../_x509sign_lib.py", "../layer/layer_host.h", "../rec/rec_wave.h",
+                                             "../rec/rec_place.h"]))
+    src, plan, place = read["x509sign.hip"], read["x509sign_plan.h"], read["../rec/rec_place.h"]
+    certificate_helpers_shared_once("x509sign")
+    for h in ("../layer/layer_host.h", "../rec/rec_place.h", "../x509/x509_dev.h", "../../include/mldsa_x509sign.h", "x509sign_plan.h"):
         assert f'#include "{h}"' in src, h
     assert '#include "../rec/rec_plan.h"' in plan and '#include "../x509/x509_plan.h"' in plan
     # the kernel boundary does the ordering: no atomics, no flag another workgroup waits for, no host wait; the scaffold is shared, not copied
@@ -220,7 +221,7 @@ def test_kernels_do_not_spill_and_sources_are_clean(lib):
     # the plan has no HIP in it, and the kernels keep no second copy of its rules, of the TLV reader or of the wave copy
     code = re.sub(r"//[^\n]*", "", plan)
     assert "hip" not in code.lower() and "__device__" not in plan and "__global__" not in plan and "constexpr" in plan
-    kernel_code = re.sub(r"//[^\n]*", "", src)
+    kernel_code = re.sub(r"//[^\n]*", "", src + place)  # (the scan is rec_place.h's, which libmldsa_csr.so shares)
     for call in ("entry_status(", "walk_tbs(", "cert_len(", "header_byte(", "trailer_byte(", "in_range(", "copy_field(", "wave_inclusive("):
         assert call in kernel_code, call
     for word in ("0x30", "0x82", "0x0B", "0xA0", "65535", "0x11"):  # the rules and the frame live in the plan alone
